@@ -4,7 +4,15 @@ solve -> G2P) of the BASELINE.json config-2 stand-in (63^3-ce
 fp64, 3 MG levels, -lsolver 3 -smoother 5 -coarseSolver 2 --project --linesearch --bcproject --usecn).
 
 Prints ONE JSON line on rank 0.  `value` = ms per nonlinear (L-BFGS) iteration, Hessian + hierarchy build excluded
-(reported separately and amortised); extra keys carry the P2G+G2P Mparticles/s half of the metric.
+(reported separately and amortised); `ms_per_step` = wall time of one timed step.  A plain run sets up, warms up, times
+--steps steps and prints the line; everything below that takes runs of its own (the profiled pass behind `roofline`, `transfers` and
+`kernel_ms_per_step_top`, the measured copy bandwidth, `cpu_baseline`) runs only with --full; without it those keys are null, and so is
+`p2g_g2p_mparticles_per_s`, the P2G+G2P Mparticles/s half of the metric.
+--dump-outputs DIR writes what the timed path returns after its last step (hot_get_particles: X, V, C, F, mu, lam, Jp in the caller's
+particle order, float64 or float32 as the configuration) as DIR/<name>.npy; a body of more than DUMP_PARTICLES particles is written as a
+fixed, seeded sample of them.  The inputs are seeded (hot_amd/synth.py): two builds given the same arguments can be compared file by file.
+The outputs themselves move from run to run with the order of the P2G scatter's atomics (iteration counts included): a
+difference between two builds means something only beyond the spread between two runs of one build.
 `roofline` = the kernel (device symbol) with the largest share of the timed region, from HIP events recorded on the
 library's launch stream (hot_config.profile); its `avg_launch_ms` is what rocprofv3 --kernel-trace --stats reports
 for the same symbol (profiles/).  `cpu_baseline` = the CPU oracle (a port of the reference's TBB decomposition to
@@ -124,6 +132,20 @@ def make_ctx(lib, cloud, cfg, device=0, profile=0, comm=None, **over):
     return ctx
 
 
+DUMP_PARTICLES = 1 << 18  # 27 reals per particle: 57 MB at fp64, within the 64 MB a dump may take
+
+
+def dump_outputs(ctx, out_dir):
+    """--dump-outputs: the particle state a caller receives after the last timed step, one .npy per hot_get_particles array.  Larger
+    bodies are sampled: DUMP_PARTICLES particle indices drawn with a fixed seed, ascending, the same for every run with the same arguments."""
+    p = ctx.get_particles()
+    n = p["X"].shape[0]
+    idx = np.arange(n) if n <= DUMP_PARTICLES else np.sort(np.random.default_rng(0).choice(n, DUMP_PARTICLES, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in p.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[idx]))
+
+
 def algorithmic_bytes(name, s, Np, levels, launches_per_half_sweep=8.0):
     """SURVEY.md §8(d) per-launch algorithmic (compulsory) bytes of one profile record; None if not modelled."""
     base, _, lv = name.rpartition("_L")
@@ -227,7 +249,15 @@ def parse_args():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"], help="N > 1: weak = the body grows so that every GPU keeps the configuration's particle count (default); "
                     "strong = the configuration's own body (e.g. --config C4 --gpus 4: BASELINE's 16 M particles over four GPUs), every rank generating only its cell planes")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks on device 0 (functional check of the N > 1 path on a one-GPU box, not a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="one GPU: after the timed steps also run the profiled pass (roofline, transfers, per-kernel table, "
+                    "measured copy bandwidth) and, unless --no-cpu, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the particle state after the last timed step as DIR/<name>.npy (one GPU only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def _spawned(rank, world, port, argv):
@@ -310,6 +340,8 @@ def main():
     ctx.sync()
     barrier()
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, dist, "cuda")
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs)
 
     iters = sum(st["iterations"] for st in stats)
     build_ms = sum(st["ms_hessian"] + st["ms_mg_build"] for st in stats)
@@ -322,7 +354,7 @@ def main():
     used_fallback_comm = hasattr(ctx, "_fallback_comm")
     if world == 1:
         del ctx  # the timed context's device memory goes before the profiled one is created (C5's whole body: two of them do not fit 288 GB)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         pctx = make_ctx(lib, cloud, cfg, device=local, profile=1)
         pctx.advance(dt)
         pctx.profile_reset()
@@ -402,7 +434,7 @@ def main():
     # headline configuration itself — one whole time step per variant, same inputs, same solver knobs — in two variants
     # (SURVEY.md §8d): "faithful" leaves serial what the reference leaves serial, "fair" parallelises those sections too.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         import subprocess
         # the checker is rebuilt here, on the host that times it: -march=native must mean THIS machine's cores
         rebuilt = subprocess.call(["make", "-s", "-B", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"]) == 0

@@ -14,7 +14,7 @@ P2="SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_LDS_BANK_CONFLI
 i=0
 for P in "$P1" "$P2"; do
     i=$((i+1))
-    (cd /tmp && timeout 900 rocprofv3 --pmc $P --output-format csv -d "$OUT/sq_${CFG}_$i" -o pmc -- python $ROOT/bench.py --config $CFG --steps 1 --warmup 0 --no-cpu > "$OUT/sq_${CFG}_$i.json" 2> "$OUT/sq_${CFG}_$i.err")
+    (cd /tmp && timeout 900 rocprofv3 --pmc $P --output-format csv -d "$OUT/sq_${CFG}_$i" -o pmc -- python $ROOT/bench.py --config $CFG --full --steps 1 --warmup 0 --no-cpu > "$OUT/sq_${CFG}_$i.json" 2> "$OUT/sq_${CFG}_$i.err")
 done
 python profiles/summarize_pmc.py "$OUT/sq_${CFG}_summary.json" "$OUT/sq_${CFG}_1" "$OUT/sq_${CFG}_2"
 find "$OUT" -name "*counter_collection.csv" -delete

@@ -2,7 +2,7 @@
 # usage: ab.sh "ENV1=.. ENV2=.." ...   -> one bench line summary per setting
 for setting in "$@"; do
   echo "== $setting"
-  env $setting timeout 300 python bench.py --no-cpu --steps 2 2>/dev/null | python -c "
+  env $setting timeout 300 python bench.py --full --no-cpu --steps 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('ms/iter', round(d['value'],3), 'ms/step', round(d['ms_per_step'],1), 'it/step', d['iterations_per_step'], 'build', round(d['hessian_mg_build_ms_per_step'],1))

@@ -3,7 +3,7 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/pmc_C4; mkdir -p "$OUT"; export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-    (cd /tmp && timeout 1500 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python $ROOT/bench.py --config C4 --steps 1 --warmup 0 --no-cpu > "$OUT/pmc_$C.json" 2> "$OUT/pmc_$C.err")
+    (cd /tmp && timeout 1500 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_$C" -o pmc -- python $ROOT/bench.py --config C4 --full --steps 1 --warmup 0 --no-cpu > "$OUT/pmc_$C.json" 2> "$OUT/pmc_$C.err")
 done
 python profiles/summarize_pmc.py "$OUT/pmc_summary.json" "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE"
 find "$OUT" -name "*counter_collection.csv" -delete

@@ -1,4 +1,4 @@
-// A/B build only (-DHOT_AB_KERNELS, libhotmi355x_ab.so): included by ../mg_solve.hip inside `#ifdef HOT_AB_KERNELS`; not part of the product library.
+// A/B build only (-DHOT_AB_KERNELS, libhotmi355x_ab.so): included by ../mg_gs.hip inside `#ifdef HOT_AB_KERNELS`; not part of the product library.
 // First-generation kernels and launch-structure alternatives that tests/test_gpu_variants.py and the tools compare the production kernels with.
 // One colour of one half-sweep of symmetric block GS.  FWD: h_i = Dinv (rhs_i - sum_{j<i} A_ij h_j), also writes
 // hD_i = D_i h_i ; BWD: du_i = Dinv (rhs_i - sum_{j>i} A_ij du_j).  "<" is the packed (colour, block, index) key.

@@ -243,7 +243,7 @@ __device__ inline void block_sum_256_n(double (&v)[NV], Use use, double* smn)
 // deposit is ordered before the counter increment by s_waitcnt vmcnt(0) (the store has been acknowledged by then).  A
 // release / acquire pair would be the portable spelling, but at agent scope it compiles to buffer_wbl2 + buffer_inv, which
 // flush and invalidate the XCD's whole L2 once per workgroup (measured: k_state 0.25 -> 0.65 ms at 37 k workgroups).
-// The same hardware-level hand-off is used by k_gs_sweep (mg_solve.hip).  The counter is left at 0 for the next launch on
+// The same hardware-level hand-off is used by k_gs_sweep (mg_gs.hip).  The counter is left at 0 for the next launch on
 // the stream.  t0 / t1: block totals, valid in thread 0 (block_sum_256).
 struct GridRed {
     double* part; // >= 2 * gridDim.x

@@ -1,5 +1,5 @@
 // libhotmi355x — typed context.  Member functions are defined in sort.hip / transfer.hip / force.hip /
-// hessian.hip / mg_build.hip / mg_solve.hip / solve.hip and explicitly instantiated there for float and double.
+// hessian.hip / mg_build.hip / mg_solve.hip / mg_gs.hip / solve.hip and explicitly instantiated there for float and double.
 #pragma once
 #include "hot_ctx.h"
 #include <atomic>
@@ -20,6 +20,30 @@ struct GsImg {
     static constexpr size_t cap_entries = 1340 + 1; // + the all-zero entry 0
     static constexpr size_t per_dir = cap_entries * 9, per_block = hdr_elems + 2 * per_dir;
     static constexpr size_t idx_per_dir = 64 * 64; // 16-bit entry indices [row][step of the direction's walk] (0 = no entry in that column: the all-zero entry)
+};
+
+// How smooth_dev runs the symmetric block-GS sweeps of a level (Ctx::gs_plan, mg_gs.hip).  Evaluated at every use, never kept: it follows the
+// chained path's switch-off (gs_no_chain: a time-out, several ranks), what hot_build_mg prepared on the level, hot_config and the A/B switches.
+struct GsPlan {
+    enum Path {
+        CHAINED, // one k_gs_sweep launch per half sweep, its passes handed off inside the launch
+        COLOUR, // one k_gs_colour launch per colour (one rank, levels with images and the four slot lists)
+        PAIR, // k_gs_offblock + k_gs_subst per colour (levels with images and the two slot lists)
+        PER_COLOUR, // one k_gs_block launch per colour (nmerge sub-blocks each)
+        SIMPLE, // A/B build, HOT_SIMPLE_GS: one k_gs_color launch per colour
+    } path;
+    int sb; // sub-block size of the block kernels: 16, 32 or 64
+    int nmerge; // sub-blocks per k_gs_block launch
+    bool winv; // CHAINED: whole-block passes on the k_gs_winv inverses
+    bool dataflag; // CHAINED: the unknowns are their own flags (else per-block sweep stamps or pass counters)
+    bool p2p; // CHAINED: point-to-point hand-off between blocks (else pass counters)
+    bool marks; // CHAINED with dataflag: the forward target (Level::tmp) takes its "not written yet" marks from the kernel before the smoother
+};
+// What split_rows (mg_build.hip) prepares on a level for the GS plan (Ctx::gs_build, mg_gs.hip, from the same helpers as gs_plan).
+struct GsBuild {
+    bool winv; // the k_gs_winv inverses of the chained path
+    bool images; // the in-block images and off-block slots of the COLOUR and PAIR paths
+    bool colour_lists; // with images: the four slot lists of k_gs_colour (else the two of k_gs_offblock)
 };
 
 // Sharded runs, hot_config.shard_owner = 0: the rank whose particle range — the SPGrid pages [split[r - 1], split[r]) of the page order — contains the
@@ -103,6 +127,13 @@ struct Level {
     DBuf<uint8_t> block_owner; // [nblocks] sharded: owner of every colour block (mark_colors orders a colour's blocks by owner, then first touch)
     std::vector<uint8_t> block_owner_h;
     std::vector<int> csplit; // [8 * (ranks + 1)] colour c: blocks color_block_begin[c] + [csplit[c][r], csplit[c][r+1]) belong to rank r
+    // the blocks [first, second) of colour c that rank `rank` of `ranks` sweeps: on a row-partitioned level its run of the colour's list, else all of them
+    std::pair<int, int> colour_run(int c, int rank, int ranks) const
+    {
+        const int b0 = color_block_begin[c];
+        if (!part) return { b0, color_block_begin[c + 1] };
+        return { b0 + csplit[c * (ranks + 1) + rank], b0 + csplit[c * (ranks + 1) + rank + 1] };
+    }
     std::vector<int> xbeg, xcnt; // [ranks * 8] position range in gs_order of the nodes rank r owns of colour c
     DBuf<int32_t> dxtab; // the same two tables on the device (xbeg | xcnt)
     int xmax_full = 0, xmax_col[8] = { 0 }; // largest per-rank counts (padded all-gather slots)
@@ -176,7 +207,7 @@ struct Ctx : CtxBase {
     void matfree_diagonal(T* dinv); // 9 Nn: inverse (Ainv) of the block diagonal of the matrix-free operator
     void assemble_tiles(Level<T>& L); // A/B build: the LDS-staged kernels of rounds 1 - 4
     void assemble_rows(Level<T>& L); // production (hessian_rows.hip)
-    void build_gs_winv(Level<T>& L); // inverse images of the in-block GS triangles of a chained level (mg_solve.hip)
+    void build_gs_winv(Level<T>& L); // inverse images of the in-block GS triangles of a chained level (mg_gs.hip)
     DBuf<int32_t> tile_tab; // its per-tile tables: [tile][64] {first particle, count} of the base cells around the tile, [tile][8] row DOFs
     // ---- atomic-free scatter: every particle group writes its (BX+2)(BY+2)(BZ+2) partial tile, then each node sums
     //      the <= 8 partial tiles that cover it in a fixed order (deterministic; global fp64 atomics top out at ~2e10/s)
@@ -534,10 +565,15 @@ struct Ctx : CtxBase {
     void estimate_2norm(Level<T>& L, double tol);
     int minres_dev(const std::function<void(const T*, T*)>& Amul, const std::function<void(const T*, T*)>& prec, T* x, const T* b, T relative_tolerance, T tolerance, int max_iterations);
     void scal(size_t n, T a, T* x); // x *= a
+    int smoother_kind(int level, bool top = false) const; // the smooth_dev kind the V-cycle runs on a level (top: its top-level solve)
+    GsPlan gs_plan(const Level<T>& L) const; // how a GS smoother sweeps the level now
+    GsBuild gs_build(const Level<T>& L) const; // what hot_build_mg prepares on the level for gs_plan
     bool gs_marks_wanted(int level) const; // the level's next smoother is the chained GS sweep that takes its forward target's "not written yet" marks from the kernel before it
     void restrict_dev(int level, const T* fine, T* coarse, T* zero_coarse = nullptr);
     void prolong_dev(int level, const T* coarse, T* fine);
     void smooth_dev(int level, int kind, int iterations, T tol, T* u, T* r, T* du, T* dAu, bool final_residual = true);
+    void gs_smooth_dev(int level, int iterations, T* u, T* r, T* du, T* dAu, bool final_residual, bool tmp_marked); // smooth_dev kind 5 (mg_gs.hip)
+    void ic_smooth_dev(Level<T>& L, T* u, T* r, T* dAu); // smooth_dev kind 7 (mg_gs.hip)
     void vcycle_dev(const T* in, T* out);
     void precondition_dev(const T* in, T* out);
     void matfree_dev(const T* x, T* y);
@@ -562,6 +598,45 @@ struct Ctx : CtxBase {
 
 // launch helpers
 inline int div_up(size_t a, size_t b) { return (int)((a + b - 1) / b); }
+
+// Row-per-wavefront kernels deal their workgroups to the XCDs in eight contiguous runs of rows (workgroup b runs on XCD b % 8: observed
+// placement, used for speed only — any placement computes the same rows): DOF ids follow the blocks in first-touch (page) order, so an
+// XCD's rows gather x from one region of the grid and that part of x stays in ITS 4 MB L2, instead of every XCD pulling all of x
+// through its own L2 (k_gs_offblock: 46 MB of 155 MB per launch were those eight copies, profiles/r04_pmc_summary.json).  Launch with
+// xcd_grid(number of workgroups).
+__device__ __forceinline__ int xcd_block() { return (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3)); }
+static inline int xcd_grid(int nwg) { return 8 * div_up(nwg, 8); }
+// A load of data a kernel reads ONCE (matrix values, column ids, images).  An ORDINARY load: the non-temporal hint, which helps a 16-byte-per-lane copy
+// (tools/micro/copy_bw.hip: 6.2 -> 6.5 TB/s), makes these 8-byte pieces — several lanes and instructions per cache line — miss on every piece: measured
+// with __builtin_nontemporal_load here, C2: the colour pass 46 -> 77 us per launch, k_gs_residual 260 -> 327 us, k_apmv_sub 183 -> 329 us.
+template <class U>
+__device__ __forceinline__ U nt_load(const U* p)
+{
+    return *p;
+}
+// "not written yet" marks of the chained GS sweeps (k_gs_sweep): signalling-NaN payloads that no arithmetic result carries
+template <class T>
+struct GsUnset;
+template <>
+struct GsUnset<double> {
+    static constexpr unsigned long long bits = 0x7ff4dead0badf00dull;
+    static __device__ __forceinline__ bool is(double v) { return (unsigned long long)__double_as_longlong(v) == bits; }
+};
+template <>
+struct GsUnset<float> {
+    static constexpr unsigned bits = 0x7fa0f00du;
+    static __device__ __forceinline__ bool is(float v) { return (unsigned)__float_as_int(v) == bits; }
+};
+template <class T>
+__device__ __forceinline__ void gs_store_unset(T* p)
+{
+    if constexpr (sizeof(T) == 8)
+        *(unsigned long long*)p = GsUnset<double>::bits;
+    else
+        *(unsigned*)p = GsUnset<float>::bits;
+}
+template <class T>
+__global__ void k_gs_fill_unset(size_t n, T* x); // x := the "not written yet" marks (mg_gs.hip)
 
 #define HOT_LAUNCH(ctx, name, kernel, grid, block, shmem, ...)                       \
     do {                                                                             \

@@ -583,7 +583,7 @@ __global__ void k_gs_pad(const int32_t* __restrict__ block_start, const int32_t*
     o[7] = (node >= 0 && rowpn) ? rowpn[node] : 0; // the share of the two off-block runs that belongs to the neighbouring colour (k_gs_slot_fill2)
 }
 
-// Off-block slots for k_gs_offblock (mg_solve.hip): a row's preceding (forward sweep) / following (backward sweep) off-block columns are cut
+// Off-block slots for k_gs_offblock (mg_gs.hip): a row's preceding (forward sweep) / following (backward sweep) off-block columns are cut
 // into runs of up to 16 stored entries, numbered over the level in (colour block, position) order — all forward slots first, then all
 // backward ones — so that every colour's slots of a direction are one contiguous range and 16-lane groups of a wavefront take one slot
 // each whatever the row lengths (3 to 98 entries a row on C2: one wavefront per row leaves more than half of its lanes without an entry).
@@ -628,7 +628,7 @@ __global__ void k_gs_slot_fill(int32_t* __restrict__ pad, const int32_t* __restr
     for (int q = 0; 16 * q < fo; ++q) slot[sb + q] = make_int2(base + kb + 16 * q, min(16, fo - 16 * q));
 }
 
-// The same slots split by the AGE of what they read (k_gs_colour, mg_solve.hip): a row's off-block run of a direction is [columns of the colour
+// The same slots split by the AGE of what they read (k_gs_colour, mg_gs.hip): a row's off-block run of a direction is [columns of the colour
 // swept just before the row's own | older colours] (forward; backward: [older | the colour just before in the backward order], k_gs_split_rows'
 // classes 0 / 1 and 5 / 6).  The older part is final one colour pass earlier and streams beside the previous colour's substitutions; the part
 // that reads the previous colour is summed by the row's own colour block.  Four lists, each numbered in (colour block, position) order:
@@ -684,7 +684,7 @@ __global__ void k_gs_slot_fill2(const int32_t* __restrict__ pad, const int32_t* 
         for (int q = 0; 16 * q < cnt[k]; ++q) slot[s[k] + q] = make_int2(base + first[k] + 16 * q, min(16, cnt[k] - 16 * q));
 }
 
-// In-block images for the finest-level GS kernels (layout: GsImg, hot_impl.h; consumer: k_gs_subst, mg_solve.hip).  One workgroup per
+// In-block images for the finest-level GS kernels (layout: GsImg, hot_impl.h; consumer: k_gs_subst, mg_gs.hip).  One workgroup per
 // colour block: (1) every row marks itself in the masks of the columns it couples to (LDS), (2) column offsets = running popcounts,
 // (3) every entry -(D_r^-1 A_rc) goes to [offset of column c + rank of r among the column's rows]; the same index, per row and step of the walk, goes to the index table.
 template <class T>
@@ -854,36 +854,24 @@ static void split_rows(Ctx<T>* ctx, Level<T>& L)
     L.gs_pad.reserve(512 * (size_t)L.nblocks + 8); // + the sentinel record of k_gs_slot_fill
     HOT_LAUNCH(ctx, "gs_pad", k_gs_pad, div_up((size_t)L.nblocks * 64, 256), 256, 0, L.gs_block_start.p, L.gs_order.p, L.rowcnt.p, L.gs_pad.p, L.nblocks, L.gs_rowpn.p);
     L.split = true;
-    // levels whose colours hold more blocks than the chip has compute units (smooth_dev: below that the chained single-launch sweep is as fast) run the off-block / substitution kernel
-    // pair, which reads the in-block couplings from premultiplied images
-    int max_nb = 0;
-    for (int c = 0; c < 8; ++c) max_nb = std::max(max_nb, L.color_block_begin[c + 1] - L.color_block_begin[c]);
-    // levels below that, swept by ONE chained launch per half sweep (smooth_dev: not row-partitioned, not forced to a launch per colour or to
-    // sub-blocks): the inverses of the blocks' in-block triangles, so that a pass is a dense product instead of a 64-step substitution
+    const GsBuild gb = ctx->gs_build(L); // what the level's GS plan (Ctx::gs_plan, mg_gs.hip) will look for
+    // chained levels: the inverses of the blocks' in-block triangles, so that a pass is a dense product instead of a 64-step substitution
     L.gs_w_ready = false;
-    // (fp64 only: in fp32 the explicit inverse is formed and applied at 6e-8 per operation, and the fp32 configurations' chained levels are the small ones)
-    {
-        const bool baseline = ctx->cfg.useBaselineMultigrid != 0;
-        const int splitLevel = ctx->cfg.topDownMGS ? 1 : ctx->cfg.levelCnt - 1;
-        const int kind = L.id < splitLevel ? (baseline ? 5 : ctx->cfg.smoother) : (baseline ? 2 : ctx->cfg.coarseSolver); // what smooth_dev runs on this level
-        // (not when the chained sweeps are switched off — a time-out, several ranks —, and never more than 2048 blocks: 290 KB of image per block in fp64,
-        // gs_chain = 2 forces the chained launch on levels of any size, which then substitute)
-        if (sizeof(T) == 8 && kind == 5 && !L.part && !ctx->gs_no_chain && ctx->cfg.gs_chain != 1 && (ctx->cfg.gs_sub_block == 0 || ctx->cfg.gs_sub_block == 64) && (max_nb <= 256 || ctx->cfg.gs_chain == 2) && L.nblocks <= 2048)
-            ctx->build_gs_winv(L);
-        if (!L.gs_w_ready && L.gs_w.p) { // the level stopped qualifying (it grew, the chain timed out): the images go
-            HOT_HIP(hipStreamSynchronize(ctx->stream));
-            HOT_HIP(hipFree(L.gs_w.p));
-            L.gs_w.p = nullptr, L.gs_w.cap = 0;
-        }
+    if (gb.winv) ctx->build_gs_winv(L);
+    if (!L.gs_w_ready && L.gs_w.p) { // the level stopped qualifying (it grew, the chain timed out): the images go
+        HOT_HIP(hipStreamSynchronize(ctx->stream));
+        HOT_HIP(hipFree(L.gs_w.p));
+        L.gs_w.p = nullptr, L.gs_w.cap = 0;
     }
+    // levels whose colours hold more blocks than the chip has compute units run the off-block / substitution kernels, which read the in-block
+    // couplings from premultiplied images
     L.gs_img_ready = false;
-    if (max_nb > 256 || ctx->cfg.gs_sub_block == 32) { // (row-partitioned levels too: the rows of other ranks have zero counts, hence no slots and empty images)
+    if (gb.images) {
         // images only for the blocks this rank owns (a row-partitioned level: one contiguous run of every colour's list; 193 KB per block in fp64)
         {
-            const int R1 = ctx->comm.size + 1, me = ctx->comm.rank;
             long long have = 0;
             for (int c = 0; c < 8; ++c) {
-                const int b0 = L.color_block_begin[c] + (L.part ? L.csplit[c * R1 + me] : 0), b1 = L.part ? L.color_block_begin[c] + L.csplit[c * R1 + me + 1] : L.color_block_begin[c + 1];
+                const auto [b0, b1] = L.colour_run(c, ctx->comm.rank, ctx->comm.size);
                 L.gs_img_shift[c] = have - b0;
                 have += b1 - b0;
             }
@@ -891,10 +879,8 @@ static void split_rows(Ctx<T>* ctx, Level<T>& L)
             L.gs_imgi.reserve(2 * GsImg<T>::idx_per_dir * (size_t)std::max<long long>(have, 1));
         }
         const int npos = 64 * L.nblocks;
-        // one rank: the colour pass is ONE launch (k_gs_colour) that needs the slots split by the age of what they read (A/B build: HOT_GS_PAIR = the
-        // kernel pair k_gs_offblock + k_gs_subst, which a row-partitioned level runs — a colour exchange sits between its passes)
         L.gs_fused_ready = false;
-        if (!L.part && !ab_flag("HOT_GS_PAIR")) {
+        if (gb.colour_lists) {
             ctx->flags.reserve(4 * (size_t)npos + 64), ctx->scan.reserve(4 * (size_t)npos);
             HOT_LAUNCH(ctx, "gs_slot_count", k_gs_slot_count2, div_up((size_t)npos, 256), 256, 0, L.gs_pad.p, ctx->flags.p, npos);
             L.gs_nslot = ctx->exclusive_scan_i32(ctx->flags.p, ctx->scan.p, 4 * (size_t)npos);
@@ -921,11 +907,9 @@ static void split_rows(Ctx<T>* ctx, Level<T>& L)
         HOT_LAUNCH(ctx, "gs_slot_fill", k_gs_slot_fill, div_up((size_t)npos + 1, 256), 256, 0, L.gs_pad.p, ctx->scan.p, L.gs_slot.p, npos, L.gs_nslot);
         { // where each colour's slots begin, per direction, for the host: k_gs_offblock gets its range as launch arguments instead of starting with a dependent load
             GsColourStarts cs;
-            const int R1 = ctx->comm.size + 1, me = ctx->comm.rank;
             for (int c = 0; c < 8; ++c) {
-                const int b0 = L.color_block_begin[c], b1 = L.color_block_begin[c + 1];
-                // a row-partitioned level: the run of the colour's block list this rank owns (Level::csplit, level_ownership)
-                cs.pos[0][c] = 64 * (L.part ? b0 + L.csplit[c * R1 + me] : b0), cs.pos[1][c] = 64 * (L.part ? b0 + L.csplit[c * R1 + me + 1] : b1);
+                const auto [b0, b1] = L.colour_run(c, ctx->comm.rank, ctx->comm.size); // (a row-partitioned level: the run of the colour's block list this rank owns)
+                cs.pos[0][c] = 64 * b0, cs.pos[1][c] = 64 * b1;
             }
             int32_t* d = (int32_t*)(ctx->flags.p); // (flags: consumed by the scan above)
             HOT_LAUNCH(ctx, "gs_slot_starts", k_gs_slot_starts, 1, 32, 0, ctx->scan.p, cs, npos, L.gs_nslot, d);
@@ -939,8 +923,7 @@ static void split_rows(Ctx<T>* ctx, Level<T>& L)
         if (!L.part) // every block, one launch (all shifts are 0)
             HOT_LAUNCH(ctx, "gs_images", k_gs_images<T>, L.nblocks, 512, 0, L.gs_col.p, L.val.p, L.gs_dinv(), L.gs_d(), L.gs_pad.p, L.gs_img.p, L.gs_imgi.p, 0);
         for (int c = 0; c < 8 && L.part; ++c) {
-            const int R1 = ctx->comm.size + 1, me = ctx->comm.rank;
-            const int b0 = L.color_block_begin[c] + L.csplit[c * R1 + me], b1 = L.color_block_begin[c] + L.csplit[c * R1 + me + 1];
+            const auto [b0, b1] = L.colour_run(c, ctx->comm.rank, ctx->comm.size);
             if (b1 > b0)
                 HOT_LAUNCH(ctx, "gs_images", k_gs_images<T>, b1 - b0, 512, 0, L.gs_col.p, L.val.p, L.gs_dinv(), L.gs_d(), L.gs_pad.p, L.gs_img.p + L.gs_img_shift[c] * (long long)GsImg<T>::per_block,
                     L.gs_imgi.p + L.gs_img_shift[c] * 2 * (long long)GsImg<T>::idx_per_dir, b0);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / LDS / spill figures of the device kernels of one HIP translation unit (cross-compiles, no GPU needed):
-#   tools/kstats.sh hot_amd/csrc/mg_solve.hip [name filter] [-DHOT_AB_KERNELS]
+#   tools/kstats.sh hot_amd/csrc/mg_gs.hip [name filter] [-DHOT_AB_KERNELS]
 src=$1; filt=${2:-.}; shift 2
 d=$(dirname $src)
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics -ffp-contract=fast -Wno-unused-result -Wno-unused-value -Wno-pass-failed "$@" \

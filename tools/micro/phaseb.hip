@@ -1,4 +1,4 @@
-// Micro-benchmark of the block-GS substitution phase (mg_solve.hip gs_phase_b): lane = row, SB steps, per step one LDS column of 3x3
+// Micro-benchmark of the block-GS substitution phase (mg_gs.hip gs_phase_b): lane = row, SB steps, per step one LDS column of 3x3
 // blocks, a broadcast of the finished row and nine FP64 FMAs.  Variants of the broadcast / layout, timed in isolation on one wavefront per
 // workgroup (what the kernel does while the other waves idle).   hipcc --offload-arch=gfx950 -O3 phaseb.hip -o phaseb && ./phaseb
 #include <hip/hip_runtime.h>

@@ -25,7 +25,7 @@ class hot_config(C.Structure):
         ("useCN", C.c_int32), ("project", C.c_int32), ("systemBCProject", C.c_int32), ("linesearch", C.c_int32),
         ("matrixFree", C.c_int32), ("boundaryType", C.c_int32), ("useAdaptiveHessian", C.c_int32),
         ("topDownMGS", C.c_int32), ("max_iterations", C.c_int32), ("plasticity", C.c_int32),
-        ("yield_stress", C.c_double), ("snow", C.c_double * 5), ("profile", C.c_int32), ("debug_store", C.c_int32), ("useBaselineMultigrid", C.c_int32), ("gs_chain", C.c_int32), ("gs_sub_block", C.c_int32), ("shard_gs", C.c_int32), ("shard_replicated", C.c_int32), ("ls_energy_only", C.c_int32), ("linear_iteration_cap", C.c_int32), ("shard_owner", C.c_int32), ("reserved", C.c_int32 * 5),
+        ("yield_stress", C.c_double), ("snow", C.c_double * 5), ("profile", C.c_int32), ("debug_store", C.c_int32), ("useBaselineMultigrid", C.c_int32), ("gs_chain", C.c_int32), ("gs_sub_block", C.c_int32), ("shard_gs", C.c_int32), ("shard_replicated", C.c_int32), ("ls_energy_only", C.c_int32), ("linear_iteration_cap", C.c_int32), ("shard_owner", C.c_int32), ("deterministic", C.c_int32), ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -60,7 +60,7 @@ ABI_SYMBOLS = [
     "matfree_multiply", "build_mg", "get_level", "get_matrix", "get_level_nnzb", "get_prolongation", "spmv", "restrict", "prolong",
     "smooth", "vcycle", "solve", "g2p", "line_search", "should_exit", "recover_solution", "transform_residual", "compute_step", "write_partio", "write_restart", "read_restart", "set_particle_ids", "get_particle_ids", "get_stream", "set_comm", "constitutive_eval", "plasticity_eval", "advance", "calculate_dt", "advance_frame", "profile_reset", "profile_count", "profile_get", "version", "abi_version",
 ]
-ABI_VERSION = 6  # include/hot_mi355x.h HOT_ABI_VERSION: the layout of hot_config / hot_stats this module mirrors
+ABI_VERSION = 7  # include/hot_mi355x.h HOT_ABI_VERSION: the layout of hot_config / hot_stats this module mirrors
 
 
 # declared by the header for the HIP product only (device-runtime services a host-memory implementation of the ABI has no use for)

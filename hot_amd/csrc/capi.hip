@@ -69,6 +69,10 @@ int hot_create(const hot_config* cfg, hot_ctx** out)
         fprintf(stderr, "libhotmi355x: hot_create: hot_config.shard_owner must be 0 (by the sweep), 1 (first touch) or 2 (page range), shard_gs 0 (colour-synchronous), 1 (rank-local) or 2 (rank-local, l1-scaled)\n");
         return HOT_ERR_INVALID;
     }
+    if (cfg->deterministic != 0 && cfg->deterministic != 1) {
+        fprintf(stderr, "libhotmi355x: hot_create: hot_config.deterministic must be 0 (atomic scatters) or 1 (bitwise-reproducible steps), got %d\n", (int)cfg->deterministic);
+        return HOT_ERR_INVALID;
+    }
     hot_ctx* c = new hot_ctx;
     try {
         c->impl = cfg->dtype == 0 ? hot::make_ctx_f32(*cfg) : hot::make_ctx_f64(*cfg);

@@ -748,12 +748,120 @@ __global__ __launch_bounds__(256) void k_force_cells2(const T* __restrict__ X, c
     for (int t = tid; t < 3 * TILE; t += THREADS) out[t] = (T)(&acc[0][0])[t];
 }
 
+// ---- deterministic mode (hot_config.deterministic = 1): the force scatter without floating-point atomics, k_p2g_det's structure (transfer.hip) with
+// k_force_cells2's items: the (cell, row, half) item sums of a chunk are stored into a slab with one writer per slot, and every tile node adds the
+// entries of the <= 27 cells around it in a fixed order.  Also the scatter of the deterministic matrix-free product (per-particle matrices from
+// k_matfree_stress_det, scale = -dt^2).
+template <class T>
+__global__ __launch_bounds__(256) void k_force_det(const T* __restrict__ X, const T* __restrict__ stress, int64_t Np, const int32_t* __restrict__ group_first,
+    const int32_t* __restrict__ group_origin, const int32_t* __restrict__ group_cell0, const int32_t* __restrict__ cell_first, T* __restrict__ part, T one_over_dx, T scale)
+{
+    using G = Geo<T>;
+    constexpr int TY = G::BY + 2, TZ = G::BZ + 2, TILE = (G::BX + 2) * TY * TZ, THREADS = 256, CH = 256;
+    static_assert(TILE <= THREADS, "one thread per tile node");
+    using AT = AccT<T>;
+    __shared__ T sp[12][CH]; // scale * S(9), x(3)
+    __shared__ T slab[3][G::EPB][27];
+    __shared__ int32_t segs[G::EPB];
+    __shared__ int32_t stamp[G::EPB];
+    __shared__ int32_t nseg;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int first = group_first[g], last = group_first[g + 1], c0 = group_cell0[g], c1 = group_cell0[g + 1];
+    const int ox = group_origin[3 * g], oy = group_origin[3 * g + 1], oz = group_origin[3 * g + 2];
+    const int nz = tid % TZ, ny = (tid / TZ) % TY, nx = tid / (TZ * TY);
+    AT acc[3] = { (AT)0, (AT)0, (AT)0 };
+    if (tid < G::EPB) stamp[tid] = 0;
+    for (int ch = first, n = 1; ch < last; ch += CH, ++n) {
+        if (tid == 0) nseg = 0;
+        __syncthreads();
+        for (int l = tid; l < CH && ch + l < last; l += THREADS) {
+            const int64_t p = ch + l;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) sp[c][l] = scale * stress[(int64_t)c * Np + p];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) sp[9 + d][l] = X[(int64_t)d * Np + p];
+        }
+        for (int c = c0 + tid; c < c1; c += THREADS) {
+            const int s0 = max(cell_first[c], ch), s1 = min(cell_first[c + 1], min(ch + CH, last));
+            if (s1 > s0) segs[atomicAdd(&nseg, 1)] = (s0 - ch) | ((s1 - ch) << 16); // a list only: the sums do not follow its order
+        }
+        __syncthreads();
+        const int ni = nseg * 6;
+        for (int it = tid; it < ni; it += THREADS) {
+            const int sd = segs[it / 6], j = (it % 6) >> 1, hf = it & 1, s0 = sd & 0xffff, s1 = sd >> 16;
+            const int mid = (s0 + s1 + 1) >> 1, l0 = hf ? mid : s0, l1 = hf ? s1 : mid;
+            T a[3][3][3]; // [i][k][component]
+#pragma unroll
+            for (int e = 0; e < 27; ++e) (&a[0][0][0])[e] = (T)0;
+            const int b0 = base_node_of<T>(one_over_dx, sp[9][s0]), b1 = base_node_of<T>(one_over_dx, sp[10][s0]), b2 = base_node_of<T>(one_over_dx, sp[11][s0]);
+            for (int l = l0; l < l1; ++l) { // the arithmetic of k_force_cells2's items
+                int e0, e1, e2;
+                T wx[3], dwx[3], wy3[3], dwy3[3], wz[3], dwz[3];
+                bspline<T>(one_over_dx, sp[9][l], e0, wx, dwx);
+                bspline<T>(one_over_dx, sp[10][l], e1, wy3, dwy3);
+                bspline<T>(one_over_dx, sp[11][l], e2, wz, dwz);
+                const T wy = j == 0 ? wy3[0] : (j == 1 ? wy3[1] : wy3[2]), dwy = j == 0 ? dwy3[0] : (j == 1 ? dwy3[1] : dwy3[2]);
+                T S[9];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) S[c] = sp[c][l];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const T wi = wx[i], dwi = one_over_dx * dwx[i];
+                    const T wij = wi * wy, dwij_i = dwi * wy, dwij_j = wi * one_over_dx * dwy;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const T g0 = dwij_i * wz[k], g1 = dwij_j * wz[k], g2 = wij * one_over_dx * dwz[k];
+                        a[i][k][0] += -(S[0] * g0 + S[3] * g1 + S[6] * g2);
+                        a[i][k][1] += -(S[1] * g0 + S[4] * g1 + S[7] * g2);
+                        a[i][k][2] += -(S[2] * g0 + S[5] * g1 + S[8] * g2);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 27; ++e) (&a[0][0][0])[e] += dpp_move<0xb1, 0xf>((&a[0][0][0])[e]); // both lanes of the pair hold the same sums
+            const int cl = ((b0 - ox) << (G::yb + G::zb)) | ((b1 - oy) << G::zb) | (b2 - oz);
+#pragma unroll
+            for (int e = 0; e < 27; ++e) {
+                const int ik = e / 3, q = e % 3, i = ik / 3, k = ik % 3;
+                if ((e < 14) == (hf == 0)) slab[q][cl][(i * 3 + j) * 3 + k] = (&a[0][0][0])[e];
+            }
+            if (hf == 0 && j == 0) stamp[cl] = n;
+        }
+        __syncthreads();
+        if (tid < TILE) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const int cx = nx - i, cy = ny - j, cz = nz - k;
+                        if ((unsigned)cx < (unsigned)G::BX && (unsigned)cy < (unsigned)G::BY && (unsigned)cz < (unsigned)G::BZ) {
+                            const int cl = (cx << (G::yb + G::zb)) | (cy << G::zb) | cz;
+                            if (stamp[cl] == n) {
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) acc[q] += (AT)slab[q][cl][(i * 3 + j) * 3 + k];
+                            }
+                        }
+                    }
+        }
+    }
+    if (tid < TILE) {
+        T* out = part + (int64_t)g * 3 * TILE;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) out[q * TILE + tid] = (T)acc[q];
+    }
+}
+
 // rasterizeForceToTVStack from the stresses the last k_state left behind (the line search needs it once, at the accepted
 // point: lineSearch evaluates only the energy per trial, ImplicitSolver.h:312-333)
 template <class T>
 void Ctx<T>::force_pass()
 {
     int64_t slots = (int64_t)Nb * EPB;
+    if (cfg.deterministic) // fixed-order sums (overrides the A/B build's HOT_FORCE_* switches)
+        HOT_LAUNCH(this, "force_scatter_det", k_force_det<T>, Ng, 256, 0, pX.p, pStress.p, Np, group_first.p, group_origin.p, group_cell0.p, cell_first.p, gPart.p, (T)1 / dx, dt);
+    else
 #ifdef HOT_AB_KERNELS
     if (ab_flag("HOT_FORCE_V1")) // one LDS atomic per particle, node and component
         HOT_LAUNCH(this, "force_scatter", k_force_scatter<T>, Ng, 256, 0, pX.p, pStress.p, Np, group_first.p, group_origin.p, group_nb.p, gPart.p, (T)1 / dx, dt);
@@ -1070,6 +1178,66 @@ __global__ __launch_bounds__(256) void k_matfree(const T* __restrict__ X, const 
     T* out = part + (int64_t)g * 3 * TILE;
     for (int t = threadIdx.x; t < 3 * TILE; t += 256) out[t] = (T)(&acc[0][0])[t];
 }
+// deterministic mode: the per-particle half of k_matfree — S_p = V_p dP(Fn^T grad x) Fn^T, written per particle (column-major, [9][Np]) instead of
+// scattered; k_force_det then scatters -dt^2 S_p like a stress, in a fixed order
+template <class T>
+__global__ __launch_bounds__(256) void k_matfree_stress_det(const T* __restrict__ X, const T* __restrict__ Fn, const T* __restrict__ Ft, const T* __restrict__ Vol, const T* __restrict__ Mu,
+    const T* __restrict__ Lam, int64_t Np, const int32_t* __restrict__ group_first, const int32_t* __restrict__ group_origin, const int32_t* __restrict__ group_nb,
+    const int32_t* __restrict__ gIdx, const T* __restrict__ x, T* __restrict__ out, T one_over_dx, int project)
+{
+    using G = Geo<T>;
+    constexpr int TY = G::BY + 2, TZ = G::BZ + 2, TILE = (G::BX + 2) * TY * TZ;
+    __shared__ T nv[3][TILE];
+    __shared__ int32_t nb8[8];
+    const int g = blockIdx.x;
+    if (threadIdx.x < 8) nb8[threadIdx.x] = group_nb[g * 8 + threadIdx.x];
+    __syncthreads();
+    for (int t = threadIdx.x; t < TILE; t += 256) {
+        int idx = gIdx[tile_slot2<T>(t, nb8)];
+        T a = 0, b = 0, c = 0;
+        if (idx >= 0) a = x[3 * idx], b = x[3 * idx + 1], c = x[3 * idx + 2];
+        nv[0][t] = a, nv[1][t] = b, nv[2][t] = c;
+    }
+    __syncthreads();
+    const int first = group_first[g], last = group_first[g + 1];
+    const int ox = group_origin[3 * g], oy = group_origin[3 * g + 1], oz = group_origin[3 * g + 2];
+    for (int p = first + threadIdx.x; p < last; p += 256) {
+        T xp[3] = { X[p], X[Np + p], X[2 * Np + p] };
+        int base[3];
+        T w[3][3], dw[3][3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) bspline<T>(one_over_dx, xp[d], base[d], w[d], dw[d]);
+        const int cx = base[0] - ox, cy = base[1] - oy, cz = base[2] - oz;
+        Mat3<T> gx;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) gx.a[c] = (T)0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    T g0 = one_over_dx * dw[0][i] * w[1][j] * w[2][k], g1 = w[0][i] * one_over_dx * dw[1][j] * w[2][k], g2 = w[0][i] * w[1][j] * one_over_dx * dw[2][k];
+                    int t = ((cx + i) * TY + (cy + j)) * TZ + (cz + k);
+                    T v0 = nv[0][t], v1 = nv[1][t], v2 = nv[2][t];
+                    gx.a[0] += v0 * g0, gx.a[1] += v1 * g0, gx.a[2] += v2 * g0;
+                    gx.a[3] += v0 * g1, gx.a[4] += v1 * g1, gx.a[5] += v2 * g1;
+                    gx.a[6] += v0 * g2, gx.a[7] += v1 * g2, gx.a[8] += v2 * g2;
+                }
+        Mat3<T> Fo, Fc;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Fo.a[c] = Fn[(int64_t)c * Np + p], Fc.a[c] = Ft[(int64_t)c * Np + p];
+        HessBlocks<T> h;
+        corotated_hessian(Fc, Mu[p], Lam[p], project != 0, h);
+        Mat3<T> dP = hess_apply(h, m3_mul(gx, Fo));
+        T vol = Vol[p];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) out[(int64_t)(c * 3 + r) * Np + p] = vol * (dP(r, 0) * Fo(c, 0) + dP(r, 1) * Fo(c, 1) + dP(r, 2) * Fo(c, 2));
+    }
+}
+
 template <class T>
 __global__ void k_matfree_finish(const T* __restrict__ gOut, const int32_t* __restrict__ dofSlot, const T* __restrict__ mass, const T* __restrict__ x, T* y, int nn, int64_t slots)
 {
@@ -1087,8 +1255,15 @@ void Ctx<T>::matfree_dev(const T* x, T* y)
     DBuf<T>& tile = ap; // scratch tile array (3*slots); `ap` is otherwise only used while building the hierarchy
     tile.reserve(3 * slots);
     if (halo_mode()) halo_gather(*levels[0], const_cast<T*>(x)); // x at the nodes of this rank's particle tiles
-    HOT_LAUNCH(this, "matfree_hessian_product", k_matfree<T>, Ng, 256, 0, pX.p, pFn.p, pFt.p, pVol.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_nb.p, gIdx.p, x, gPart.p, dx,
-        (T)1 / dx, dt, cfg.project);
+    if (cfg.deterministic) { // per-particle matrices, then the fixed-order force scatter
+        pMfS.reserve(9 * (size_t)Np);
+        HOT_LAUNCH(this, "matfree_stress_det", k_matfree_stress_det<T>, Ng, 256, 0, pX.p, pFn.p, pFt.p, pVol.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_nb.p, gIdx.p, x, pMfS.p,
+            (T)1 / dx, cfg.project);
+        HOT_LAUNCH(this, "matfree_hessian_product_det", k_force_det<T>, Ng, 256, 0, pX.p, pMfS.p, Np, group_first.p, group_origin.p, group_cell0.p, cell_first.p, gPart.p, (T)1 / dx, -dt * dt);
+    }
+    else
+        HOT_LAUNCH(this, "matfree_hessian_product", k_matfree<T>, Ng, 256, 0, pX.p, pFn.p, pFt.p, pVol.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_nb.p, gIdx.p, x, gPart.p, dx,
+            (T)1 / dx, dt, cfg.project);
     reduce_tiles(3, tile.p, tile.p + slots, tile.p + 2 * slots, nullptr, nullptr, "matfree_reduce");
     if (halo_mode()) {
         T* arr[3] = { tile.p, tile.p + slots, tile.p + 2 * slots };

@@ -198,13 +198,13 @@ void Ctx<T>::build_hessian()
         color_level(*L);
         level_ownership(*L);
     }
-    const bool v1 = ab_flag("HOT_HESSIAN_V1"); // A/B build only: per-cell global-atomic scatter kernel
+    const bool v1 = ab_flag("HOT_HESSIAN_V1") && !cfg.deterministic; // A/B build only: per-cell global-atomic scatter kernel (deterministic mode: never)
     HOT_LAUNCH(this, "hessian_fill_cols", k_fill_cols<T>, div_up(ne, 256), 256, 0, block_map, gIdx.p, id2coord.p, mass.p, L->col.p, L->val.p, Nn, v1 ? 1 : 0);
 #ifdef HOT_AB_KERNELS
     if (v1)
         HOT_LAUNCH(this, "hessian_assemble_v1", k_hessian<T>, Ng, 256, 0, pX.p, pFn.p, pFt.p, pVol.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_nb.p, gIdx.p, L->val.p, dx, (T)1 / dx,
             dt, cfg.project);
-    else if (ab_flag("HOT_HESSIAN_TILES") || ab_flag("HOT_HESSIAN_TILES_V1") || ab_flag("HOT_HESSIAN_MFMA"))
+    else if (!cfg.deterministic && (ab_flag("HOT_HESSIAN_TILES") || ab_flag("HOT_HESSIAN_TILES_V1") || ab_flag("HOT_HESSIAN_MFMA")))
         assemble_tiles(*L); // rounds 2 - 4: particle chunks staged in LDS
     else
 #endif

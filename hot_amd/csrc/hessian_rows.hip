@@ -229,7 +229,7 @@ template <class T>
 struct RowsPre { // the wavefront's records in flight: on entry of a walk [0] = its record 0, [1] = its record 1 (valid if cnt > 1)
     T r[3][2];
 };
-template <class T, int NR>
+template <class T, int NR, bool DET = false> // DET: the wavefront owns the rows it walks (k_hessian_rows_det): plain read-modify-write flush, no float atomics
 __device__ __forceinline__ void hr_walk(const T* __restrict__ rp /*wave-uniform*/, int cnt, const T* __restrict__ nrp, int ncnt, RowsPre<T>& P, const RowsTask& tk, T* __restrict__ stage,
     AccT<T>* __restrict__ tile, int lane, const RowsLane& ld)
 {
@@ -314,9 +314,16 @@ __device__ __forceinline__ void hr_walk(const T* __restrict__ rp /*wave-uniform*
             if (r < nrow) { // wave-uniform
                 const int row = qs[r];
                 AT* o = tile + row * 1125 + ((tk.lx0 + (row >> 2) - ld.j0 + 2) * 25 + (tk.ly0 + ((row >> 1) & 1) - ld.j1 + 2) * 5 + (tk.lz0 + (row & 1) - ld.j2 + 2)) * 9 + 4 * ld.h;
-                if (ld.h == 0) lds_atomic_add(o, (AT)acc[r][0]);
+                if constexpr (DET) {
+                    if (ld.h == 0) o[0] += (AT)acc[r][0];
 #pragma unroll
-                for (int e = 1; e < 5; ++e) lds_atomic_add(o + e, (AT)acc[r][e]);
+                    for (int e = 1; e < 5; ++e) o[e] += (AT)acc[r][e];
+                }
+                else {
+                    if (ld.h == 0) lds_atomic_add(o, (AT)acc[r][0]);
+#pragma unroll
+                    for (int e = 1; e < 5; ++e) lds_atomic_add(o + e, (AT)acc[r][e]);
+                }
             }
         }
     }
@@ -534,6 +541,100 @@ __global__ __launch_bounds__(RowsLds<T>::THREADS) void k_hessian_rows(const T* _
 #endif
 }
 
+// ---- deterministic mode (hot_config.deterministic = 1): rows owned exclusively.  Eight wavefronts, wavefront r owns row r of the tile: it walks the
+// cells of the row's 3x3x3 support in ascending order of their index in the 4x4x4 neighbourhood, each cell's particles in sort order (hr_walk with
+// one row: K formed once per (particle, row), the broadcast FMAs), and flushes its accumulators after each cell with a plain read-modify-write of
+// the LDS tile, which no other wavefront writes.  No task counter, no float atomics: every entry is summed in an order the data fixes.  Each
+// particle record is loaded once per row instead of once per (cell, x-plane) task.  Same tables, same write-out and the same sharded own / written
+// semantics as k_hessian_rows.
+template <class T>
+__global__ __launch_bounds__(512) void k_hessian_rows_det(const T* __restrict__ rec, const int2* __restrict__ tcell, const int32_t* __restrict__ trow, const T* __restrict__ mass, T* __restrict__ val, int ntiles,
+    const uint8_t* __restrict__ own, uint8_t* __restrict__ written)
+{
+    using AT = AccT<T>;
+    constexpr int THREADS = 512;
+    extern __shared__ __attribute__((aligned(16))) char hr_smem[];
+    AT* tile = (AT*)hr_smem; // [8][1125]
+    T* stages = (T*)(tile + 8 * 1125); // [8][REC]
+    int32_t* cstart = (int32_t*)(stages + 8 * REC); // [64]
+    int32_t* ccnt = cstart + 64; // [64]
+    int32_t* rdof = ccnt + 64; // [8]
+    int32_t* ctl = rdof + 8; // [0]: some cell with particles lies in the support of an active row
+    const int tid = threadIdx.x;
+    const int id = blockIdx.x, run = (id & 7) + 8 * (id >> 8), tile_id = run * 32 + ((id >> 3) & 31);
+    if (tile_id >= ntiles) return;
+    if (tid < 8) rdof[tid] = trow[(int64_t)tile_id * 8 + tid];
+    if (tid >= 64 && tid < 128) {
+        const int2 fc = tcell[(int64_t)tile_id * 64 + (tid - 64)];
+        cstart[tid - 64] = fc.x, ccnt[tid - 64] = fc.y;
+    }
+    for (int e = tid; e < 8 * 1125; e += THREADS) tile[e] = (AT)0;
+    __syncthreads();
+    bool any = false;
+    for (int r = 0; r < 8; ++r) any = any || rdof[r] >= 0;
+    if (!any) return;
+    const int lane = tid & 63, row = tid >> 6;
+    // the cells of this wavefront's row: lane = cell of the 4x4x4 neighbourhood, inside the row's support and holding particles
+    unsigned long long cells = 0;
+    {
+        const int ox = (lane >> 4) - 2, oy = ((lane >> 2) & 3) - 2, oz = (lane & 3) - 2;
+        const bool in = rdof[row] >= 0 && (unsigned)((row >> 2) - ox) < 3u && (unsigned)(((row >> 1) & 1) - oy) < 3u && (unsigned)((row & 1) - oz) < 3u && ccnt[lane] > 0;
+        cells = __ballot(in);
+    }
+    if (tid == 0) ctl[0] = 0;
+    __syncthreads();
+    if (lane == 0 && cells) ctl[0] = 1; // (any writer writes 1)
+    __syncthreads();
+    if (own) { // sharded: as k_hessian_rows, a tile none of whose rows this rank owns and none of whose cells hold particles of its shard is skipped
+        bool mine = false;
+        for (int r = 0; r < 8; ++r) mine = mine || (rdof[r] >= 0 && own[rdof[r]]);
+        if (!mine && ctl[0] == 0) return; // workgroup-uniform
+    }
+    const RowsLane ld = rows_lane(lane);
+    T* stage = stages + row * REC;
+    if (cells) { // wave-uniform
+        auto range = [&](int cell, const T*& rp, int& cnt) {
+            rp = rec + (int64_t) __builtin_amdgcn_readfirstlane(cstart[cell]) * REC, cnt = __builtin_amdgcn_readfirstlane(ccnt[cell]);
+        };
+        int cell = __builtin_ffsll((long long)cells) - 1, cnt;
+        cells &= cells - 1;
+        const T* rp;
+        range(cell, rp, cnt);
+        RowsPre<T> P;
+        P.r[0][0] = rp[lane], P.r[0][1] = rp[64 + lane];
+        {
+            const T* q = rp + (cnt > 1 ? REC : 0);
+            P.r[1][0] = q[lane], P.r[1][1] = q[64 + lane];
+        }
+        while (true) {
+            int ncell = cell, ncnt = 1;
+            const T* nrp = rp;
+            const bool more = cells != 0;
+            if (more) {
+                ncell = __builtin_ffsll((long long)cells) - 1;
+                cells &= cells - 1;
+                range(ncell, nrp, ncnt);
+            }
+            const RowsTask tk = { -((cell >> 4) - 2), -(((cell >> 2) & 3) - 2), -((cell & 3) - 2), 1 << row };
+            hr_walk<T, 1, true>(rp, cnt, nrp, ncnt, P, tk, stage, tile, lane, ld);
+            if (!more) break;
+            cell = ncell, rp = nrp, cnt = ncnt;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < 8 * 1125; e += THREADS) {
+        int r = e / 1125, q = e - r * 1125;
+        int dof = rdof[r];
+        if (dof < 0) continue;
+        T v = (T)tile[e];
+        if (q >= 62 * 9 && q < 63 * 9 && ((q - 62 * 9) % 4 == 0) && (!own || own[dof])) v += mass[dof]; // inertia term on the diagonal slot (ImplicitSolver.h:486-496)
+        val[(int64_t)dof * 1125 + q] = v;
+        if (written && q == 0) written[dof] = 1;
+    }
+}
+template <class T>
+constexpr size_t kRowsDetLds = (size_t)8 * 1125 * sizeof(AccT<T>) + (size_t)8 * REC * sizeof(T) + (size_t)(64 * 2 + 8 + 8) * sizeof(int32_t);
+
 template <class T>
 void Ctx<T>::assemble_rows(Level<T>& L)
 {
@@ -553,8 +654,17 @@ void Ctx<T>::assemble_rows(Level<T>& L)
     int2* tcell = (int2*)tile_tab.p;
     int32_t* trow = tile_tab.p + (size_t)ntiles * 128;
     HOT_LAUNCH(this, "hessian_tile_cells", k_tile_cells<T>, div_up((int64_t)ntiles * 64, 256), 256, 0, blocks.p, gIdx.p, cell_first.p, cell_map, tcell, trow, ntiles);
-    HOT_LAUNCH(this, "hessian_assemble", k_hessian_rows<T>, 256 * div_up(ntiles, 256), RowsLds<T>::THREADS, RowsLds<T>::bytes, pDP.p, tcell, trow, mass.p, L.val.p, ntiles, L.mask(),
-        L.part ? written.p : (uint8_t*)nullptr);
+    if (cfg.deterministic) { // rows owned by one wavefront each (overrides the A/B build's HOT_HESSIAN_* switches, hessian.hip)
+        if (!attr_rows_det_set) {
+            HOT_HIP(hipFuncSetAttribute((const void*)k_hessian_rows_det<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsDetLds<T>));
+            attr_rows_det_set = true;
+        }
+        HOT_LAUNCH(this, "hessian_assemble_det", k_hessian_rows_det<T>, 256 * div_up(ntiles, 256), 512, kRowsDetLds<T>, pDP.p, tcell, trow, mass.p, L.val.p, ntiles, L.mask(),
+            L.part ? written.p : (uint8_t*)nullptr);
+    }
+    else
+        HOT_LAUNCH(this, "hessian_assemble", k_hessian_rows<T>, 256 * div_up(ntiles, 256), RowsLds<T>::THREADS, RowsLds<T>::bytes, pDP.p, tcell, trow, mass.p, L.val.p, ntiles, L.mask(),
+            L.part ? written.p : (uint8_t*)nullptr);
 #ifdef HOT_HT_CLOCKS
     std::vector<unsigned long long> hall(65536 * 8);
     unsigned long long hc[8] = {};

@@ -209,6 +209,69 @@ __global__ __launch_bounds__(256) void k_mf_diag_col(const T* __restrict__ X, co
     T* out = part + (int64_t)g * 3 * TILE;
     for (int t = threadIdx.x; t < 3 * TILE; t += 256) out[t] = (T)(&acc[0][0])[t];
 }
+// deterministic mode: the same column by owner-computes gathers.  One workgroup per particle group; each tile node, one thread, walks the <= 27
+// cells of the page around it in the order of its kernel index (i, j, k) and each cell's particles in sort order, and sums what k_mf_diag_col adds
+// by LDS atomics.  Off the default path (lsolver 1 / 2 with matrixFree): correctness first, no staging.
+template <class T>
+__global__ __launch_bounds__(256) void k_mf_diag_det(const T* __restrict__ X, const T* __restrict__ Fn, const T* __restrict__ dp, int64_t Np, const int32_t* __restrict__ group_first,
+    const int32_t* __restrict__ group_origin, const int32_t* __restrict__ group_cell0, const int32_t* __restrict__ cell_first, T* __restrict__ part, T one_over_dx, int cc)
+{
+    using G = Geo<T>;
+    constexpr int TY = G::BY + 2, TZ = G::BZ + 2, TILE = (G::BX + 2) * TY * TZ;
+    static_assert(TILE <= 256, "one thread per tile node");
+    using AT = AccT<T>;
+    __shared__ int32_t cstart[G::EPB], cend[G::EPB]; // particle range of each cell of the page (empty: start == end)
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int c0 = group_cell0[g], c1 = group_cell0[g + 1];
+    const int ox = group_origin[3 * g], oy = group_origin[3 * g + 1], oz = group_origin[3 * g + 2];
+    if (tid < G::EPB) cstart[tid] = 0, cend[tid] = 0;
+    __syncthreads();
+    for (int c = c0 + tid; c < c1; c += 256) {
+        const int f = cell_first[c];
+        const int b0 = base_node_of<T>(one_over_dx, X[f]), b1 = base_node_of<T>(one_over_dx, X[Np + f]), b2 = base_node_of<T>(one_over_dx, X[2 * Np + f]);
+        const int cl = ((b0 - ox) << (G::yb + G::zb)) | ((b1 - oy) << G::zb) | (b2 - oz);
+        cstart[cl] = f, cend[cl] = cell_first[c + 1];
+    }
+    __syncthreads();
+    if (tid >= TILE) return;
+    const int nz = tid % TZ, ny = (tid / TZ) % TY, nx = tid / (TZ * TY);
+    AT acc[3] = { (AT)0, (AT)0, (AT)0 };
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            for (int k = 0; k < 3; ++k) {
+                const int cx = nx - i, cy = ny - j, cz = nz - k;
+                if ((unsigned)cx >= (unsigned)G::BX || (unsigned)cy >= (unsigned)G::BY || (unsigned)cz >= (unsigned)G::BZ) continue;
+                const int cl = (cx << (G::yb + G::zb)) | (cy << G::zb) | cz;
+                for (int p = cstart[cl]; p < cend[cl]; ++p) {
+                    int base[3];
+                    T w[3][3], dw[3][3];
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) bspline<T>(one_over_dx, X[(int64_t)d * Np + p], base[d], w[d], dw[d]);
+                    const T wi = i == 0 ? w[0][0] : (i == 1 ? w[0][1] : w[0][2]), dwi = i == 0 ? dw[0][0] : (i == 1 ? dw[0][1] : dw[0][2]);
+                    const T wj = j == 0 ? w[1][0] : (j == 1 ? w[1][1] : w[1][2]), dwj = j == 0 ? dw[1][0] : (j == 1 ? dw[1][1] : dw[1][2]);
+                    const T wk = k == 0 ? w[2][0] : (k == 1 ? w[2][1] : w[2][2]), dwk = k == 0 ? dw[2][0] : (k == 1 ? dw[2][1] : dw[2][2]);
+                    const T g0 = one_over_dx * dwi * wj * wk, g1 = wi * one_over_dx * dwj * wk, g2 = wi * wj * one_over_dx * dwk;
+                    T F9[9], gi[3];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) F9[c] = Fn[(int64_t)c * Np + p];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) gi[c] = F9[c * 3] * g0 + F9[c * 3 + 1] * g1 + F9[c * 3 + 2] * g2;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        T v = (T)0;
+#pragma unroll
+                        for (int q = 0; q < 3; ++q)
+#pragma unroll
+                            for (int vv = 0; vv < 3; ++vv) v += dp[(int64_t)sym45(a + 3 * vv, cc + 3 * q) * Np + p] * gi[vv] * gi[q];
+                        acc[a] += (AT)v;
+                    }
+                }
+            }
+    T* out = part + (int64_t)g * 3 * TILE;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[a * TILE + tid] = (T)acc[a];
+}
+
 template <class T>
 __global__ void k_mf_diag_finish(const T* __restrict__ tile /*[9][slots]: column-major blocks*/, const int32_t* __restrict__ dofSlot, const T* __restrict__ mass, T* __restrict__ dinv, int nn,
     int64_t slots, int Ainv)
@@ -241,7 +304,10 @@ void Ctx<T>::matfree_diagonal(T* dinv)
     DBuf<T>& tile = ap; // scratch (9 * slots)
     tile.reserve(9 * slots);
     for (int cc = 0; cc < 3; ++cc) {
-        HOT_LAUNCH(this, "matfree_diag_scatter", k_mf_diag_col<T>, Ng, 256, 0, pX.p, pFn.p, pDP.p, Np, group_first.p, group_origin.p, gPart.p, (T)1 / dx, cc);
+        if (cfg.deterministic)
+            HOT_LAUNCH(this, "matfree_diag_scatter_det", k_mf_diag_det<T>, Ng, 256, 0, pX.p, pFn.p, pDP.p, Np, group_first.p, group_origin.p, group_cell0.p, cell_first.p, gPart.p, (T)1 / dx, cc);
+        else
+            HOT_LAUNCH(this, "matfree_diag_scatter", k_mf_diag_col<T>, Ng, 256, 0, pX.p, pFn.p, pDP.p, Np, group_first.p, group_origin.p, gPart.p, (T)1 / dx, cc);
         reduce_tiles(3, tile.p + (3 * cc) * slots, tile.p + (3 * cc + 1) * slots, tile.p + (3 * cc + 2) * slots, nullptr, nullptr, "matfree_diag_reduce");
     }
     if (halo_mode()) {

@@ -202,6 +202,7 @@ struct Ctx : CtxBase {
     DBuf<unsigned long long> ch_rank;
     DBuf<int32_t> ch_id;
     HashMap cell_map; // (Linear_Offset(base cell) >> data_bits) -> cell id
+    DBuf<T> pMfS; // deterministic matrix-free product: 9*Np per-particle matrices V_p dP Fn^T (force.hip)
     DBuf<T> pDP; // Hessian assembly: 64*Np particle records (k_dpdf_rec, hessian_rows.hip); matrix-free diagonal: 45*Np symmetric 9x9 V_p dt^2 dP/dF
     void build_cell_table();
     void matfree_diagonal(T* dinv); // 9 Nn: inverse (Ainv) of the block diagonal of the matrix-free operator
@@ -379,7 +380,7 @@ struct Ctx : CtxBase {
     bool attr_cg_set = false;
     int cg_group = 2; // iterations the last fused top-level PCG took: size of the first group of launches of the next one
     int gs_epoch = 0; // sweep number, never reused inside a context
-    bool attr_tiles_set = false, attr_rows_set = false, attr_gs_set = false, attr_winv_set = false; // dynamic-LDS limits raised on this context's device (hipFuncSetAttribute is per device)
+    bool attr_tiles_set = false, attr_rows_set = false, attr_rows_det_set = false, attr_gs_set = false, attr_winv_set = false; // dynamic-LDS limits raised on this context's device (hipFuncSetAttribute is per device)
     DBuf<int> gs_done; // [0,40) pass counters of k_gs_sweep (the sticky wait-timeout flag lives in pinned host memory, hscal[250])
     double* hscal = nullptr; // pinned host mirror
     // ---- L-BFGS history
@@ -465,9 +466,14 @@ struct Ctx : CtxBase {
         if (retry_scope > 0 && !gs_no_chain && ab_int("HOT_GS_FAKE_TIMEOUT", 0) > 0 && ++fake_syncs == ab_int("HOT_GS_FAKE_TIMEOUT", 0)) *(volatile int*)(hscal + 250) = 1;
         if (*(volatile int*)(hscal + 250) != 0) {
             *(volatile int*)(hscal + 250) = 0;
-            gs_no_chain = gs_chain_timed_out = true;
             cg_bar_dirty = true; // a k_cg_persist workgroup that gave up did not re-arm the barrier counters: cleared before the next persistent launch (after rearm_chain)
             ++gs_timeouts, steps_since_timeout = 0;
+            if (cfg.deterministic) { // one launch per pass associates differently: redo with the same structure, never switch silently
+                if (gs_timeouts > MAX_TIMEOUTS)
+                    throw Error{ HOT_ERR_DEVICE, "deterministic mode: a chained Gauss-Seidel sweep or persistent PCG timed out more than 3 times on this context; the launch-per-pass fallback would change the bits, so the operation fails" };
+                throw Error{ ERR_RETRY, "k_gs_sweep: wait on a neighbouring block timed out; deterministic mode: redoing the operation with the same launch structure" };
+            }
+            gs_no_chain = gs_chain_timed_out = true;
             throw Error{ ERR_RETRY, "k_gs_sweep: wait on a neighbouring block timed out; redoing the operation with one launch per pass" };
         }
     }
@@ -479,13 +485,18 @@ struct Ctx : CtxBase {
             Scope(int& n_) : n(n_) { ++n; }
             ~Scope() { --n; }
         } scope(retry_scope);
-        try {
-            fn();
+        for (;;) {
+            try {
+                fn();
+                return;
+            }
+            catch (const Error& e) {
+                if (e.code != ERR_RETRY) throw;
+                if (!cfg.deterministic) break;
+                // deterministic mode: the same structure again, from the saved inputs; sync() turns the time-out after MAX_TIMEOUTS into HOT_ERR_DEVICE
+            }
         }
-        catch (const Error& e) {
-            if (e.code != ERR_RETRY) throw;
-            fn(); // gs_no_chain is set now: no chained sweep can occur, so this cannot throw ERR_RETRY again
-        }
+        fn(); // gs_no_chain is set now: no chained sweep can occur, so this cannot throw ERR_RETRY again
     }
     int32_t exclusive_scan_i32(const int32_t* in, int32_t* out, size_t n); // returns total (syncs)
     void need(bool cond, const char* what) { HOT_CHECK(cond, HOT_ERR_INVALID, what); }

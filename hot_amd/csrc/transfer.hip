@@ -290,6 +290,138 @@ __global__ __launch_bounds__(256) void k_p2g_stream(const T* __restrict__ X, con
 #endif
 }
 
+// ---- deterministic mode (hot_config.deterministic = 1): P2G without floating-point atomics.  One workgroup per particle group, its particles in chunks
+// of CH staged in LDS.  The items are k_p2g_stream's — (cell segment, node row j, half of the segment), the nine nodes (i, k) of the row and all NQ
+// quantities summed in registers in the particles' sort order, the two halves added by a DPP move (a + b == b + a) — but the pair STORES its sums
+// into the chunk's slab at (quantity, cell of the page, i, j, k) instead of adding them to the tile: every slot has one writer (a cell appears once per
+// chunk).  Then every tile node, one thread each, adds the slab entries of the <= 27 cells around it, in a fixed order, to sums in its own registers.
+// The order of every node sum is chunk, cell coordinates, particle sort order: fixed by the data, whatever the wavefronts' timing.  The partial tile
+// goes through k_tile_reduce like the atomic kernel's.
+template <class T, bool WITH_CN>
+__global__ __launch_bounds__(256) void k_p2g_det(const T* __restrict__ X, const T* __restrict__ V, const T* __restrict__ M, const T* __restrict__ C, const T* __restrict__ Mu,
+    const T* __restrict__ Lam, int64_t Np, const int32_t* __restrict__ group_first, const int32_t* __restrict__ group_origin, const int32_t* __restrict__ group_cell0,
+    const int32_t* __restrict__ cell_first, T* __restrict__ part, T dx, T one_over_dx)
+{
+    using G = Geo<T>;
+    constexpr int TY = G::BY + 2, TZ = G::BZ + 2, TILE = (G::BX + 2) * TY * TZ;
+    constexpr int NQ = WITH_CN ? 5 : 4, NS = 16 + (WITH_CN ? 1 : 0), CH = 256, THREADS = 256;
+    static_assert(TILE <= THREADS, "one thread per tile node");
+    using AT = AccT<T>;
+    __shared__ T sp[NS][CH];
+    __shared__ T slab[NQ][G::EPB][27]; // item sums (T, as they leave the registers) by cell of the page and node (i, j, k) of its kernel
+    __shared__ int32_t segs[G::EPB];
+    __shared__ int32_t stamp[G::EPB]; // chunk ordinal that last wrote the cell's slab entries
+    __shared__ int32_t nseg;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int first = group_first[g], last = group_first[g + 1], c0 = group_cell0[g], c1 = group_cell0[g + 1];
+    const int ox = group_origin[3 * g], oy = group_origin[3 * g + 1], oz = group_origin[3 * g + 2];
+    const int nz = tid % TZ, ny = (tid / TZ) % TY, nx = tid / (TZ * TY); // this thread's tile node
+    AT acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = (AT)0;
+    if (tid < G::EPB) stamp[tid] = 0;
+    for (int ch = first, n = 1; ch < last; ch += CH, ++n) {
+        if (tid == 0) nseg = 0;
+        __syncthreads(); // the previous chunk's node sums are done with sp / slab / segs
+        for (int l = tid; l < CH && ch + l < last; l += THREADS) {
+            const int64_t p = ch + l;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) sp[d][l] = X[(int64_t)d * Np + p], sp[4 + d][l] = V[(int64_t)d * Np + p];
+            const T m = M[p];
+            sp[3][l] = m;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) sp[7 + c][l] = C[(int64_t)c * Np + p];
+            if constexpr (WITH_CN) {
+                const T mu = Mu[p], la = Lam[p];
+                sp[NS - 1][l] = m * hsqrt((T)3 * ((T)2 * mu + la) * ((T)2 * mu + la) + (T)6 * la * la + (T)12 * mu * mu);
+            }
+        }
+        for (int c = c0 + tid; c < c1; c += THREADS) {
+            const int s0 = max(cell_first[c], ch), s1 = min(cell_first[c + 1], min(ch + CH, last));
+            if (s1 > s0) segs[atomicAdd(&nseg, 1)] = (s0 - ch) | ((s1 - ch) << 16); // a list only: the sums do not follow its order
+        }
+        __syncthreads();
+        const int n6 = nseg * 6; // even: the two lanes of a (segment, row) pair are active together
+        for (int it = tid; it < n6; it += THREADS) {
+            const int sd = segs[it / 6], j = (it % 6) >> 1, hf = it & 1, s0 = sd & 0xffff, s1 = sd >> 16;
+            const int mid = (s0 + s1 + 1) >> 1, l0 = hf ? mid : s0, l1 = hf ? s1 : mid;
+            T a[3][3][NQ]; // [i][k][quantity]
+#pragma unroll
+            for (int e = 0; e < 9 * NQ; ++e) (&a[0][0][0])[e] = (T)0;
+            const int b0 = base_node_of<T>(one_over_dx, sp[0][s0]), b1 = base_node_of<T>(one_over_dx, sp[1][s0]), b2 = base_node_of<T>(one_over_dx, sp[2][s0]);
+            const T fb0 = (T)b0, fb1 = (T)b1, fb2 = (T)b2;
+            for (int l = l0; l < l1; ++l) { // the arithmetic of k_p2g_stream's items
+                const T x0 = sp[0][l], x1 = sp[1][l], x2 = sp[2][l];
+                auto w3 = [&](T x, T fb, T(&w)[3]) {
+                    const T d0 = fma(one_over_dx, x, -fb);
+                    const T z = (T)1.5 - d0, d1 = d0 - (T)1, zz = (T)1.5 - ((T)1 - d1);
+                    w[0] = (T)0.5 * z * z, w[1] = (T)0.75 - d1 * d1, w[2] = (T)0.5 * zz * zz;
+                };
+                T wi[3], wj3[3], wk[3];
+                w3(x0, fb0, wi), w3(x1, fb1, wj3), w3(x2, fb2, wk);
+                const T wj = j == 0 ? wj3[0] : (j == 1 ? wj3[1] : wj3[2]);
+                const T d1 = (T)(b1 + j) * dx - x1;
+                const T m = sp[3][l];
+                T cn = (T)0, u3[3], cc[3], ee[3];
+                if constexpr (WITH_CN) cn = sp[NS - 1][l];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) u3[q] = sp[10 + q][l] * d1 + sp[4 + q][l], cc[q] = sp[7 + q][l], ee[q] = sp[13 + q][l];
+                T d0[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) d0[i] = (T)(b0 + i) * dx - x0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const T d2 = (T)(b2 + k) * dx - x2, wjk = wj * wk[k], mwjk = m * wjk;
+                    T t[3];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) t[q] = ee[q] * d2 + u3[q];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const T mw = wi[i] * mwjk;
+                        a[i][k][0] += mw;
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) a[i][k][1 + q] += (cc[q] * d0[i] + t[q]) * mw;
+                        if constexpr (WITH_CN) a[i][k][NQ - 1] += cn * (wi[i] * wjk);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 9 * NQ; ++e) (&a[0][0][0])[e] += dpp_move<0xb1, 0xf>((&a[0][0][0])[e]); // both lanes of the pair now hold the same sums
+            const int cl = ((b0 - ox) << (G::yb + G::zb)) | ((b1 - oy) << G::zb) | (b2 - oz);
+            constexpr int H = (9 * NQ + 1) / 2; // the even lane stores sums 0 .. H - 1, the odd lane the rest
+#pragma unroll
+            for (int e = 0; e < 9 * NQ; ++e) {
+                const int ik = e / NQ, q = e % NQ, i = ik / 3, k = ik % 3;
+                if ((e < H) == (hf == 0)) slab[q][cl][(i * 3 + j) * 3 + k] = (&a[0][0][0])[e];
+            }
+            if (hf == 0 && j == 0) stamp[cl] = n;
+        }
+        __syncthreads();
+        if (tid < TILE) { // node sums: the cells (nx - i, ny - j, nz - k) of the page in the order of (i, j, k)
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const int cx = nx - i, cy = ny - j, cz = nz - k;
+                        if ((unsigned)cx < (unsigned)G::BX && (unsigned)cy < (unsigned)G::BY && (unsigned)cz < (unsigned)G::BZ) {
+                            const int cl = (cx << (G::yb + G::zb)) | (cy << G::zb) | cz;
+                            if (stamp[cl] == n) {
+#pragma unroll
+                                for (int q = 0; q < NQ; ++q) acc[q] += (AT)slab[q][cl][(i * 3 + j) * 3 + k];
+                            }
+                        }
+                    }
+        }
+    }
+    if (tid < TILE) {
+        T* out = part + (int64_t)g * NQ * TILE;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) out[q * TILE + tid] = (T)acc[q];
+    }
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void k_block_count(const T* __restrict__ gM, int32_t* block_count, int nb)
 {
@@ -354,6 +486,13 @@ void Ctx<T>::p2g()
     int64_t slots = (int64_t)Nb * EPB;
     T one_over_dx = (T)1 / dx;
     const int nq = cfg.useCN ? 5 : 4;
+    if (cfg.deterministic) { // fixed-order sums (overrides the A/B build's HOT_P2G_* switches)
+        if (cfg.useCN)
+            HOT_LAUNCH(this, "p2g_det", (k_p2g_det<T, true>), Ng, 256, 0, pX.p, pV.p, pM.p, pC.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_cell0.p, cell_first.p, gPart.p, dx, one_over_dx);
+        else
+            HOT_LAUNCH(this, "p2g_det", (k_p2g_det<T, false>), Ng, 256, 0, pX.p, pV.p, pM.p, pC.p, pMu.p, pLam.p, Np, group_first.p, group_origin.p, group_cell0.p, cell_first.p, gPart.p, dx, one_over_dx);
+    }
+    else
 #ifdef HOT_AB_KERNELS
     if (ab_flag("HOT_P2G_V1")) { // one LDS atomic per particle, node and quantity
         if (cfg.useCN)

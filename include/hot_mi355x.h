@@ -98,14 +98,24 @@ typedef struct hot_config {
                             rank of every cut owns all blocks the two share; 0 (default) = by the smoother: 2 under colour-synchronous sweeps (shard_gs = 0), 1 under
                             rank-local sweeps (shard_gs = 1), whose iteration counts stay within 15 % of the single-rank ones only under it (measured,
                             profiles/r05_shard_ownership.txt).  Other values are rejected */
-    int32_t reserved[5];
+    int32_t deterministic; /* 0 (default) = the scatter kernels that sum with floating-point LDS atomics, whose summation order follows wavefront timing; 1 = bitwise-reproducible
+                              time steps: given the same library build, device model, inputs, hot_config and sequence of calls, every output — particle state X, V, C, F, Jp, mu,
+                              lambda, grid arrays, assembled matrices, residuals and every hot_stats field but the ms_* timings — is bitwise identical, between two contexts of one
+                              process and between processes.  The five scatters that use float atomics otherwise (P2G with the CN quantity, force, Hessian assembly, the
+                              matrix-free product and its diagonal) run fixed-order kernels (every tile value formed by one owner, in an order the data fixes), coarse contexts
+                              of useBaselineMultigrid inherit the flag, and a chained Gauss-Seidel sweep or persistent PCG that times out is redone with the SAME launch
+                              structure (HOT_ERR_DEVICE after the context's third time-out) instead of switching to one launch per pass.  Not claimed: bit equality with the
+                              reference or a serial build (their summation order differs), across device models or compute-unit counts (persistent kernels size their grids
+                              by it), or of the collectives of a sharded run (rank-local kernels are the fixed-order ones).  Other values are rejected.  DESIGN.md §11 */
+    int32_t reserved[4];
 } hot_config;
 
 /* Version of the structures below and of hot_config: it changes whenever a field is added (fields are only ever appended).  hot_solve / hot_advance /
  * hot_advance_frame write a WHOLE hot_stats through the caller's pointer, so a caller compiled against an older header would be written past the end
  * of its structure: check hot_abi_version() == HOT_ABI_VERSION once after loading the library (hot_amd/binding.py does).
- *   5: hot_stats.comm_calls_index appended (round 5); 6: hot_config.shard_owner takes 0 / 1 / 2, hot_copy_bandwidth (round 6) */
-#define HOT_ABI_VERSION 6
+ *   5: hot_stats.comm_calls_index appended (round 5); 6: hot_config.shard_owner takes 0 / 1 / 2, hot_copy_bandwidth (round 6);
+ *   7: hot_config.deterministic takes the slot of reserved[0] (sizeof(hot_config) unchanged) */
+#define HOT_ABI_VERSION 7
 int hot_abi_version(void);
 
 typedef struct hot_stats {

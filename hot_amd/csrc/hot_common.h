@@ -182,6 +182,13 @@ __device__ __forceinline__ double dpp_move(double v)
     int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+// a wave-uniform value as the compiler can see it (scalar registers)
+__device__ __forceinline__ double wave_first(double v)
+{
+    long long b = __double_as_longlong(v);
+    int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
 __device__ __forceinline__ float wave_last(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
 __device__ __forceinline__ double wave_last(double v)
 {

@@ -853,6 +853,11 @@ __device__ unsigned long long gs_clk[34 * 8];
 // direction, row-packed planes, k_gs_winv in mg_build.hip): h = a + W a, a = D^-1 (rhs - off-block products).  The image is copied into the LDS
 // area the triangle of in-block couplings occupied (before the wait for the previous pass), every wavefront forms four rows of the product
 // (lane = column, fixed-order DPP sums) — 64 dependent broadcast-FMA steps of 150 - 190 ns become one round of ~1 us.
+// Register budget: SB = 64 runs 1024 threads, four wavefronts per SIMD, 128 registers a lane, and in fp64 the nine values of a wavefront's four rows are
+// 72 of them.  They live from the streaming (1.) to the early gathers (2a.) and no further: the slots of pass p-1 load their nine values again beside
+// the late gather (3.), a row's id and tail range sit in scalar registers (WINV) or LDS (rng), and the stamp / counter hand-offs exist in the A/B
+// build only (dflag).  Carried across both waits the values cost 55 - 66 spilled registers: 63 - 77 MB of scratch traffic per launch at C2's
+// level 1.  No instantiation has scratch (tests/test_kernel_resources.py).
 template <class T, bool FWD, int SB, bool WINV = false>
 __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict__ col, const T* __restrict__ val, const uint32_t* __restrict__ ckey, const int32_t* __restrict__ gs_order,
     const int32_t* __restrict__ block_start, const T* __restrict__ diagVal, const T* __restrict__ diagBlockInv, const T* __restrict__ rhs, T* x, T* hD, GsPasses P,
@@ -871,10 +876,17 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     // sweep; a reader of another block's unknown re-loads it until it is something else.  No flag array, no "data, wait for the
     // acknowledgement, flag" on the producer's side and no "flag, then data" round trip on the consumer's: a value is used the
     // moment it lands.  Every node is written exactly once per half sweep, so no stale value can be mistaken for a new one.
+    // (the inverse images run with the data-flag hand-off only, and so does everything outside the A/B build — gs_plan; chained_sweep checks it:
+    // the stamp and counter protocols then cost neither registers nor the look-up of 26 neighbours per workgroup)
+#ifdef HOT_AB_KERNELS
+    const bool dflag = WINV || dataflag != 0;
+#else
+    constexpr bool dflag = true;
+#endif
     auto ld3 = [&](int64_t j, T& x0, T& x1, T& x2) {
         x0 = __hip_atomic_load(x + 3 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), x1 = __hip_atomic_load(x + 3 * j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
         x2 = __hip_atomic_load(x + 3 * j + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!dataflag) return;
+        if (!dflag) return;
         int spins = 0;
         while (GsUnset<T>::is(x0) || GsUnset<T>::is(x1) || GsUnset<T>::is(x2)) {
             __builtin_amdgcn_s_sleep(2);
@@ -895,6 +907,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     const int b = P.block0[p] + ((int)blockIdx.x - P.wg_begin[p]);
     const int lo = P.sub[p] * SB;
     const int start = block_start[b] + lo, cnt = max(0, min(SB, block_start[b + 1] - start));
+    int32_t* rng = nodes + SB; // [2][SB] the tail range of every row's half (slots past the 64 kept): the substituting kernels park it here, not in registers across the waits
     T* sDinv = (T*)(nodes + 5 * SB); // [SB][9] D_i^-1 and (forward) [SB][9] D_i of the rows: fetched before the wait, so that
     T* sD = sDinv + 9 * SB; // nothing after it has to go to global memory for them
     T* srhs = sD + 9 * SB; // [SB][3] right-hand sides of the rows, likewise
@@ -942,7 +955,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
         for (int q = 0; q < RQ; ++q) {
             const int ii = w + NW * q;
             jj[q] = -1, kb2[q] = 0, ke[q] = 0, late[q] = false;
-            node[q] = ii < cnt ? nodes[ii] : -1;
+            node[q] = ii < cnt ? __builtin_amdgcn_readfirstlane(nodes[ii]) : -1; // the row id in a scalar register, and with it the class counts and the slot range
 #pragma unroll
             for (int e = 0; e < 9; ++e) bv[q][e] = (T)0;
         }
@@ -984,6 +997,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
             const int ibeg = FWD ? po : kbeg, iend = FWD ? po + pi : kbeg + fi;
             // the 64 slots kept in registers (see `head`); the rest of a longer half row is the "tail"
             kb2[q] = head ? kbeg + 64 : kbeg, ke[q] = head ? kend : kend - 64;
+            rng[ii] = kb2[q], rng[SB + ii] = ke[q]; // (every lane the same value; read back by this wavefront only)
             const int k = head ? kbeg + lane : kend - 64 + lane;
             if (k >= kbeg && k < kend) {
                 const int j = col[(int64_t)i * 125 + k];
@@ -1014,7 +1028,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     // flag index = 4 * block + sub-block.  A sub-block waits for the sub-block before it in its own block, which has waited
     // for the one before that, so a block's last sub-block in sweep order vouches for the whole block.
     int early_idx = -1, late_idx = -1; // lanes 0..27 of wavefront 0: what to see stamped before the early / the late gather
-    if (nbr && tid < 26) {
+    if (!dflag && nbr && tid < 26) { // (data flags: nobody waits for a stamp)
         const int nb = nbr[(int64_t)b * 26 + tid];
         if (nb >= 0) {
             const int cn = nb >> 28, gid = nb & 0x0fffffff;
@@ -1031,8 +1045,8 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
             }
         }
     }
-    if (nbr && tid == 26 && p > 0 && P.color[p - 1] == P.color[p]) late_idx = 4 * b + P.sub[p - 1];
-    if (nbr && tid == 27 && p > 1 && P.color[p - 2] == P.color[p]) early_idx = 4 * b + P.sub[p - 2];
+    if (!dflag && nbr && tid == 26 && p > 0 && P.color[p - 1] == P.color[p]) late_idx = 4 * b + P.sub[p - 1];
+    if (!dflag && nbr && tid == 27 && p > 1 && P.color[p - 2] == P.color[p]) early_idx = 4 * b + P.sub[p - 2];
     auto wait_blocks = [&](int idx) { // spin until that sub-block carries the current sweep number
         if (idx < 0) return;
         int spins = 0;
@@ -1044,7 +1058,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
             }
         }
     };
-    if (dataflag) {
+    if (dflag) {
     }
     else if (nbr)
         wait_blocks(early_idx);
@@ -1068,7 +1082,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
         const int ii = w + NW * q;
         tail_late[q] = false;
         if (ii >= cnt) continue; // wave-uniform
-        const int i = node[q];
+        const int i = WINV ? node[q] : nodes[ii], kt0 = WINV ? kb2[q] : rng[ii], kt1 = WINV ? ke[q] : rng[SB + ii];
         T e0 = 0, e1 = 0, e2 = 0;
         if (jj[q] >= 0 && !late[q]) {
             const int64_t j = jj[q];
@@ -1081,7 +1095,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
         // half rows longer than one wave: plain strided tail; the in-block slots come first (FWD: last) in the range, so
         // the tail may still hold sub-block couplings
         bool tl = false;
-        for (int k = kb2[q] + lane; k < ke[q]; k += 64) {
+        for (int k = kt0 + lane; k < kt1; k += 64) {
             const int j = col[(int64_t)i * 125 + k];
             const T* bb = val + ((int64_t)i * 125 + k) * 9;
             const uint32_t keyj = ckey[j], keyi = ckey[i];
@@ -1111,7 +1125,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     }
     GS_CLK(2);
     // ---- 2b. wait for the previous pass
-    if (!dataflag) {
+    if (!dflag) {
         if (nbr)
             wait_blocks(late_idx);
         else if (p > 0 && tid == 0) {
@@ -1132,22 +1146,30 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     // x of other workgroups was published with write-through stores and is read with sc1 loads below: no cache
     // maintenance (buffer_wbl2 / buffer_inv) on either side
     // ---- 3. the columns of pass p-1 against the now final unknowns
+    const T* val_again = val;
+    asm volatile("" : "+s"(val_again)); // (a pointer the compiler knows nothing about: the loads below are not merged with those of phase 1)
 #pragma unroll
     for (int q = 0; q < RQ; ++q) {
         const int ii = w + NW * q;
         if (ii >= cnt) continue; // wave-uniform
-        const int i = node[q];
+        const int i = WINV ? node[q] : nodes[ii], kt0 = WINV ? kb2[q] : rng[ii], kt1 = WINV ? ke[q] : rng[SB + ii];
         T s0 = 0, s1 = 0, s2 = 0;
         if (jj[q] >= 0 && late[q]) {
             const int64_t j = jj[q];
+            // the slot's nine values AGAIN (not carried across the waits: see the register budget above), requested together with the gather —
+            // the address was known before the wait and the line was read microseconds ago
+            const T* bb = val_again + ((int64_t)i * 125 + (head ? kt0 - 64 : kt1) + lane) * 9;
+            T bl[9];
+#pragma unroll
+            for (int e = 0; e < 9; ++e) bl[e] = bb[e];
             T x0, x1, x2;
             ld3(j, x0, x1, x2);
-            s0 = bv[q][0] * x0 + bv[q][3] * x1 + bv[q][6] * x2;
-            s1 = bv[q][1] * x0 + bv[q][4] * x1 + bv[q][7] * x2;
-            s2 = bv[q][2] * x0 + bv[q][5] * x1 + bv[q][8] * x2;
+            s0 = bl[0] * x0 + bl[3] * x1 + bl[6] * x2;
+            s1 = bl[1] * x0 + bl[4] * x1 + bl[7] * x2;
+            s2 = bl[2] * x0 + bl[5] * x1 + bl[8] * x2;
         }
         if (tail_late[q]) { // wave-uniform, rare
-            for (int k = kb2[q] + lane; k < ke[q]; k += 64) {
+            for (int k = kt0 + lane; k < kt1; k += 64) {
                 const int j = col[(int64_t)i * 125 + k];
                 const T* bb = val + ((int64_t)i * 125 + k) * 9;
                 const uint32_t keyj = ckey[j], keyi = ckey[i];
@@ -1215,7 +1237,7 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     if (cnt > 0) gs_phase_b<T, FWD, SB, true>(tri, sv, nodes, cnt, lane, diagVal, diagBlockInv, x, hD, sD);
     GS_CLK_OUT();
     // ---- publish: the write-through stores of every lane have left the CU before lane 0 bumps the pass counter
-    if (dataflag) return; // the write-through stores of phase B are the publication
+    if (dflag) return; // the write-through stores of phase B are the publication
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) {
         if (nbr)
@@ -1654,6 +1676,9 @@ void Ctx<T>::gs_smooth_dev(int level, int iterations, T* u, T* r, T* du, T* dAu,
             HOT_HIP(hipMemsetAsync(gs_done.p, 0, 40 * sizeof(int), stream));
         const int grid = P.wg_begin[P.npass];
         const int dataflag = plan.dataflag ? 1 : 0;
+#ifndef HOT_AB_KERNELS
+        HOT_CHECK(dataflag, HOT_ERR_INVALID, "k_gs_sweep: only the A/B build carries the stamp and pass-counter hand-offs");
+#endif
 #define HOT_GS_CASE(F, S, ...)                                                                                                                                         \
     HOT_LAUNCH(this, lname(nm, L.id).c_str(), (k_gs_sweep<T, F, S, ##__VA_ARGS__>), grid, 16 * S, (GsLds<T, S>::bytes + 21 * S * sizeof(T) + 128), L.col.p, L.val.p, L.ckey.p, L.gs_order.p, L.gs_block_start.p, \
         L.diagVal.p, L.diagBlockInv.p, rhs, xx, hD, P, rc, gs_done.p, (int*)(hscal + 250), plan.p2p ? L.gs_nbr.p : (const int32_t*)nullptr, L.gs_flag.p, gs_epoch, dataflag, \

@@ -277,10 +277,15 @@ __global__ void k_cg_direction(size_t n3, const T* __restrict__ z, T* __restrict
 // deposits its partial sum before the barrier and adds ALL deposits in index order after it, so every workgroup holds the same bits and
 // takes the same exit decision.  Same recurrences as k_cg_spmv_dot / k_cg_update / k_cg_direction; only the association of the dot
 // products differs.  count / exitc are zero between launches (the last workgroup to leave resets them).
-// RPW > 0 (round 6): a wavefront has at most RPW rows, and everything of them LIVES IN REGISTERS for the whole solve — the matrix row (lane k holds entries
-// k and k + 64: 18 scalars + 2 column ids a row), and in lane 0 D^-1, u, r, z, du, dAu.  An iteration then goes to memory for the gathers of du in the product
-// and the publication of the new du, nothing else (the streaming version walks six dependent round trips an iteration besides its three barriers: 176 us a
-// solve at C2's level 2, 5.4 k rows, of which the barriers are the smaller part).  Same arithmetic, bit-identical results.
+// RPW > 0 (round 6): a wavefront has at most RPW rows, and everything of them stays ON THE COMPUTE UNIT for the whole solve — the matrix row in registers
+// (lane k holds entries k and k + 64: 18 scalars + 2 column ids a row), D^-1, u, r, z, du, dAu of the row in 24 scalars of LDS that lane 0 works on.  An
+// iteration then goes to memory for the gathers of du in the product and the publication of the new du, nothing else (the streaming version walks six
+// dependent round trips an iteration besides its three barriers: 176 us a solve at C2's level 2, 5.4 k rows, of which the barriers are the smaller part).
+// Same arithmetic, bit-identical results.
+// Register budget: 1024 threads are four wavefronts per SIMD, 128 registers a lane; RPW = 2 in fp64 spends 76 on the matrix rows.  The rows' vectors are
+// wave-uniform: held in registers of all 64 lanes (as first written) they were 96 more, and 137 registers went to scratch memory and back every iteration.
+// What is uniform is therefore kept out of the vector registers — the wavefront's index, the recurrences' scalars (wave_first), the rows' vectors (LDS) —
+// and the kernel has no scratch (tests/test_kernel_resources.py).
 template <class T, int RPW = 0>
 __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__ col, const T* __restrict__ val, const T* __restrict__ Dinv, const T* __restrict__ init, T* __restrict__ u,
     T* __restrict__ r, T* __restrict__ z, T* du, T* __restrict__ dAu, int n, int max_iters, unsigned phase0 /*barriers this context's persistent solves have passed so far, mod 4*/, double* dep /*[4][gridDim.x][SS]*/, int SS /*doubles between two workgroups' slots*/, double* hm, double* ticket, double ticket_val,
@@ -288,7 +293,10 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
 {
     __shared__ double red[32], sres[2];
     __shared__ int s_bail;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // RPW > 0: what lane 0 of a wavefront keeps of its rows between the barriers — D^-1 and the five vectors (6 KB in fp64 beside the dynamic du)
+    enum { CG_DI = 0, CG_U = 9, CG_R = 12, CG_Z = 15, CG_D = 18, CG_AD = 21 };
+    __shared__ T cg_row[RPW > 0 ? 16 : 1][RPW > 0 ? RPW : 1][24];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6); // (the wavefront's index, hence its rows and their addresses, in scalar registers)
     const int G = gridDim.x, wg = blockIdx.x;
     unsigned phase = phase0;
     if (tid == 0) s_bail = 0;
@@ -345,7 +353,7 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
         }
         __syncthreads();
         if (s_bail) return false; // workgroup-uniform
-        o0 = sres[0], o1 = sres[1];
+        o0 = wave_first(sres[0]), o1 = wave_first(sres[1]); // (uniform, and known to be: the scalars of the recurrences stay out of the vector registers)
         ++phase;
         return true;
     };
@@ -355,10 +363,12 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
     };
     const int stride = 16 * G;
     if constexpr (RPW > 0) {
-        // ---- the register-resident version
+        // ---- the register-resident version.  Register budget: 1024 threads = four wavefronts per SIMD = 128 registers a lane, of which the matrix rows
+        // take 2 x (18 scalars + a column id) = 76 in fp64.  A row's vectors and D^-1 are wave-uniform and lane 0's business only: they live in the
+        // wavefront's own 24 scalars of LDS per row (cg_row: D^-1, u, r, z, du, dAu), not in a register of every lane
         int rowq[RPW];
         int32_t mc[RPW][2];
-        T mv[RPW][2][9], di[RPW][9], uu[RPW][3], rr[RPW][3], zz[RPW][3], dd[RPW][3], ad[RPW][3];
+        T mv[RPW][2][9];
         double p0 = 0, p1 = 0;
 #pragma unroll
         for (int q = 0; q < RPW; ++q) {
@@ -372,20 +382,23 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
 #pragma unroll
                 for (int e = 0; e < 9; ++e) mv[q][h][e] = (lane + 64 * h < 125) ? val[rc * 1125 + k * 9 + e] : (T)0;
             }
+            if (lane == 0) {
+                T* st = cg_row[w][q];
+                T di[9], a[3], za[3], rr[3], zz[3];
 #pragma unroll
-            for (int e = 0; e < 9; ++e) di[q][e] = Dinv[9 * rc + e];
-            T a[3], za[3];
+                for (int e = 0; e < 9; ++e) di[e] = Dinv[9 * rc + e], st[CG_DI + e] = di[e];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a[c] = init[3 * rc + c], rr[q][c] = r[3 * rc + c], uu[q][c] = u[3 * rc + c], ad[q][c] = (T)0;
+                for (int c = 0; c < 3; ++c) a[c] = init[3 * rc + c], rr[c] = r[3 * rc + c], st[CG_U + c] = u[3 * rc + c], st[CG_AD + c] = (T)0;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) za[c] = di[q][c] * a[0] + di[q][3 + c] * a[1] + di[q][6 + c] * a[2], zz[q][c] = di[q][c] * rr[q][0] + di[q][3 + c] * rr[q][1] + di[q][6 + c] * rr[q][2];
-            if (lane == 0 && rowq[q] >= 0) {
-                p0 += (double)(za[0] * a[0]) + (double)(za[1] * a[1]) + (double)(za[2] * a[2]);
-                p1 += (double)(zz[q][0] * rr[q][0]) + (double)(zz[q][1] * rr[q][1]) + (double)(zz[q][2] * rr[q][2]);
-                for (int c = 0; c < 3; ++c) sdu(row, c, zz[q][c]);
+                for (int c = 0; c < 3; ++c) za[c] = di[c] * a[0] + di[3 + c] * a[1] + di[6 + c] * a[2], zz[c] = di[c] * rr[0] + di[3 + c] * rr[1] + di[6 + c] * rr[2];
+                if (rowq[q] >= 0) {
+                    p0 += (double)(za[0] * a[0]) + (double)(za[1] * a[1]) + (double)(za[2] * a[2]);
+                    p1 += (double)(zz[0] * rr[0]) + (double)(zz[1] * rr[1]) + (double)(zz[2] * rr[2]);
+                    for (int c = 0; c < 3; ++c) sdu(row, c, zz[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) st[CG_R + c] = rr[c], st[CG_Z + c] = zz[c], st[CG_D + c] = zz[c];
             }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dd[q][c] = zz[q][c];
         }
         double zTr0, zTr;
         if (!all_sum(p0, p1, zTr0, zTr)) return;
@@ -404,8 +417,8 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
                 double2 v[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const int e = min(e0 + k * 1024 + tid, n16 - 1);
-                    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=v"(v[k]) : "v"((const double2*)du + e) : "memory");
+                    const unsigned eb = 16u * (unsigned)min(e0 + k * 1024 + tid, n16 - 1); // (scalar base + 32-bit offset: one address register a load, not two)
+                    asm volatile("global_load_dwordx4 %0, %1, %2 sc0 sc1" : "=v"(v[k]) : "v"(eb), "s"(du) : "memory");
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -447,8 +460,11 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
                     }
                 }
                 s0 = wave_sum(s0), s1 = wave_sum(s1), s2 = wave_sum(s2);
-                ad[q][0] = s0, ad[q][1] = s1, ad[q][2] = s2;
-                if (lane == 0 && rowq[q] >= 0) pd += (double)(s0 * dd[q][0]) + (double)(s1 * dd[q][1]) + (double)(s2 * dd[q][2]);
+                if (lane == 0) {
+                    T* st = cg_row[w][q];
+                    st[CG_AD] = s0, st[CG_AD + 1] = s1, st[CG_AD + 2] = s2;
+                    if (rowq[q] >= 0) pd += (double)(s0 * st[CG_D]) + (double)(s1 * st[CG_D + 1]) + (double)(s2 * st[CG_D + 2]);
+                }
             }
             CG_TK(1);
             double dAd, unused;
@@ -457,25 +473,35 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
             const double omega = zTr / dAd;
             const T wp = (T)omega, wm = (T)(-omega);
             double pz = 0;
+            if (lane == 0) {
 #pragma unroll
-            for (int q = 0; q < RPW; ++q) {
+                for (int q = 0; q < RPW; ++q) {
+                    T* st = cg_row[w][q];
+                    T rr[3], zz[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) uu[q][c] += wp * dd[q][c], rr[q][c] = rr[q][c] + wm * ad[q][c];
+                    for (int c = 0; c < 3; ++c) st[CG_U + c] += wp * st[CG_D + c], rr[c] = st[CG_R + c] + wm * st[CG_AD + c];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) zz[q][c] = di[q][c] * rr[q][0] + di[q][3 + c] * rr[q][1] + di[q][6 + c] * rr[q][2];
-                if (lane == 0 && rowq[q] >= 0) pz += (double)(zz[q][0] * rr[q][0]) + (double)(zz[q][1] * rr[q][1]) + (double)(zz[q][2] * rr[q][2]);
+                    for (int c = 0; c < 3; ++c) zz[c] = st[CG_DI + c] * rr[0] + st[CG_DI + 3 + c] * rr[1] + st[CG_DI + 6 + c] * rr[2];
+                    if (rowq[q] >= 0) pz += (double)(zz[0] * rr[0]) + (double)(zz[1] * rr[1]) + (double)(zz[2] * rr[2]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) st[CG_R + c] = rr[c], st[CG_Z + c] = zz[c];
+                }
             }
             CG_TK(3);
             double zTrNew;
             if (!all_sum(pz, 0.0, zTrNew, unused)) return;
             CG_TK(4);
             const T beta = (T)(zTrNew / zTr);
+            if (lane == 0) {
 #pragma unroll
-            for (int q = 0; q < RPW; ++q) {
+                for (int q = 0; q < RPW; ++q) {
+                    T* st = cg_row[w][q];
+                    T dd[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) dd[q][c] = zz[q][c] + beta * dd[q][c];
-                if (lane == 0 && rowq[q] >= 0)
-                    for (int c = 0; c < 3; ++c) sdu(rowq[q], c, dd[q][c]);
+                    for (int c = 0; c < 3; ++c) dd[c] = st[CG_Z + c] + beta * st[CG_D + c], st[CG_D + c] = dd[c];
+                    if (rowq[q] >= 0)
+                        for (int c = 0; c < 3; ++c) sdu(rowq[q], c, dd[c]);
+                }
             }
             zTr = zTrNew;
             CG_TK(5);
@@ -489,13 +515,15 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
         // what the streaming version leaves in memory: u, r, z, dAu of the last iteration (du has been published)
 #pragma unroll
         for (int q = 0; q < RPW; ++q)
-            if (lane == 0 && rowq[q] >= 0)
+            if (lane == 0 && rowq[q] >= 0) {
+                const T* st = cg_row[w][q];
                 for (int c = 0; c < 3; ++c) {
                     const int64_t e = 3 * (int64_t)rowq[q] + c;
-                    u[e] = uu[q][c], r[e] = rr[q][c], z[e] = zz[q][c], dAu[e] = ad[q][c];
+                    u[e] = st[CG_U + c], r[e] = st[CG_R + c], z[e] = st[CG_Z + c], dAu[e] = st[CG_AD + c];
                 }
+            }
         if (tid == 0 && wg == 0) {
-            hm[0] = zTr, hm[1] = (double)cnt, hm[2] = tol;
+            hm[0] = zTr, hm[1] = (double)cnt, hm[2] = tol, hm[3] = (double)(phase & 3u); // (hm[3]: the barrier set the next launch starts with — the host keeps its own count)
             if (ticket) host_ticket_store(ticket, ticket_val);
         }
         return;
@@ -573,7 +601,7 @@ __global__ __launch_bounds__(1024) void k_cg_persist(const int32_t* __restrict__
     }
     if (tid == 0) {
         if (wg == 0) {
-            hm[0] = zTr, hm[1] = (double)cnt, hm[2] = tol;
+            hm[0] = zTr, hm[1] = (double)cnt, hm[2] = tol, hm[3] = (double)(phase & 3u);
             if (ticket) host_ticket_store(ticket, ticket_val);
         }
     }
@@ -849,6 +877,7 @@ void Ctx<T>::smooth_dev(int level, int kind, int iterations, T tolerance, T* u, 
                 fprintf(stderr, "cg_persistent level %d: %d rows, %d workgroups, %d iterations; ticks pull %.0f product %.0f barrier1 %.0f update %.0f barrier2 %.0f direction %.0f barrier3 %.0f\n", L.id, L.n, G, cnt,
                     hscal[48], hscal[49], hscal[50], hscal[51], hscal[52], hscal[53], hscal[54]);
             cg_phase = (cg_phase + 1u + 3u * (unsigned)cnt) & 3u; // one barrier at the set-up, three an iteration
+            HOT_CHECK((unsigned)hscal[43] == cg_phase, HOT_ERR_DEVICE, "k_cg_persist passed another number of barriers than the host counts: the next launch would start on the wrong set of deposit slots");
             iterations = 0;
         }
         else if (fused) {

@@ -35,9 +35,7 @@ struct GsPlan {
     int sb; // sub-block size of the block kernels: 16, 32 or 64
     int nmerge; // sub-blocks per k_gs_block launch
     bool winv; // CHAINED: whole-block passes on the k_gs_winv inverses
-    bool dataflag; // CHAINED: the unknowns are their own flags (else per-block sweep stamps or pass counters)
-    bool p2p; // CHAINED: point-to-point hand-off between blocks (else pass counters)
-    bool marks; // CHAINED with dataflag: the forward target (Level::tmp) takes its "not written yet" marks from the kernel before the smoother
+    bool marks; // CHAINED: the forward target (Level::tmp) takes its "not written yet" marks from the kernel before the smoother
 };
 // What split_rows (mg_build.hip) prepares on a level for the GS plan (Ctx::gs_build, mg_gs.hip, from the same helpers as gs_plan).
 struct GsBuild {
@@ -79,10 +77,8 @@ struct Level {
     double lMin = 1e-8, lMax = 1e2; // spectrum bounds for the Chebyshev smoother (SquareMatrix.h:37, estimate2norm :375-475)
     DBuf<T> apv; // n*64*9: A*P of this level (coarse window per row, packed: the na nb nc = 27 .. 64 slots that can be non-zero come first, k_ap), kept for the coarse-correction residual update
     DBuf<int32_t> apc; // n*64: coarse column by geometric window position 16 a + 4 b + c (0 where the coarse node does not exist: its block is 0; -1 at the structurally zero positions, which apv does not store)
-    DBuf<int32_t> gs_nbr; // nblocks*26: the adjacent colour blocks (global block id | colour << 28, or -1): whose unknowns a block's rows read
-    DBuf<int> gs_flag; // 4*nblocks: sweep number in which the (block, sub-block) was last finished (k_gs_sweep's point-to-point hand-off)
     DBuf<int32_t> gs_pad; // nblocks*64*8 (+ one sentinel record): per (colour block, position) {node or -1, the row's four class counts, first forward slot, first backward slot, pad}: the GS kernels' header in one load
-    DBuf<int32_t> gs_col; // n*125: col after the regrouping with in-block columns replaced by -1 - (position in the colour block): k_gs_block2 tells triangle entries from gathers without fetching ckey[j]
+    DBuf<int32_t> gs_col; // n*125: col after the regrouping with in-block columns replaced by -1 - (position in the colour block): k_gs_images and the slot kernels (k_gs_offblock, k_gs_colour) tell in-block entries from gathers without fetching ckey[j]
     DBuf<T> gs_img; // nblocks * GsImg<T>::per_block: premultiplied in-block couplings in the order k_gs_subst consumes them (k_gs_images, mg_build.hip)
     DBuf<uint16_t> gs_imgi; // nblocks * 2 * GsImg<T>::idx_per_dir: the images' entry index of every (row, step)
     DBuf<T> gs_p1; // 3 per slot: the off-block products summed over the slot's (up to 16) entries (k_gs_offblock -> k_gs_subst, which subtracts a row's slots from its rhs in order)
@@ -379,9 +375,7 @@ struct Ctx : CtxBase {
     int cg_G = 0; // the grid the slots are laid out for
     bool attr_cg_set = false;
     int cg_group = 2; // iterations the last fused top-level PCG took: size of the first group of launches of the next one
-    int gs_epoch = 0; // sweep number, never reused inside a context
     bool attr_tiles_set = false, attr_rows_set = false, attr_rows_det_set = false, attr_gs_set = false, attr_winv_set = false; // dynamic-LDS limits raised on this context's device (hipFuncSetAttribute is per device)
-    DBuf<int> gs_done; // [0,40) pass counters of k_gs_sweep (the sticky wait-timeout flag lives in pinned host memory, hscal[250])
     double* hscal = nullptr; // pinned host mirror
     // ---- L-BFGS history
     DBuf<T> hist_dx[9], hist_dg[9];

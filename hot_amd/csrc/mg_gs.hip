@@ -3,8 +3,8 @@
 //   k_gs_block      MultigridOperator::gs_smooth (Projects/multigrid/MultigridPreconditioner.h:266-318): symmetric coloured
 //                   block Gauss–Seidel in the reference's exact node order (colour, first-touch block, id), one launch per
 //                   colour, its sub-blocks walked inside: streaming phase + LDS-triangle substitution (see the kernel).
-//   k_gs_sweep      the same passes chained inside one launch by per-block flags (coarse levels).   k_gs_color: the simple one-wavefront-
-//                   per-block version kept as the A/B reference (HOT_SIMPLE_GS).
+//   k_gs_sweep      the same passes chained inside one launch, handed off through the unknowns themselves (coarse levels).
+//   k_gs_color      the simple one-wavefront-per-block version kept as the A/B reference (HOT_SIMPLE_GS).
 #include "hot_impl.h"
 
 namespace hot {
@@ -176,7 +176,7 @@ void Ctx<T>::build_gs_winv(Level<T>& L)
 
 template <class T, bool FWD, int SB, bool WT = false>
 __device__ __forceinline__ void gs_phase_b(const T* tri, const T* sv, const int32_t* nodes, int cnt, int lane, const T* __restrict__ diagVal, const T* __restrict__ diagBlockInv, T* x, T* hD,
-    const T* ldsD = nullptr, T* ldsX = nullptr);
+    const T* ldsD = nullptr);
 
 // six waves per SIMD (three 512-thread workgroups per CU: a colour of the finest level is resident in one round) = at most 80 VGPRs
 #ifdef HOT_AB_KERNELS
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))) void 
 // write-through (sc1) stores so that other workgroups of the same launch can read it with sc1 loads
 template <class T, bool FWD, int SB, bool WT>
 __device__ __forceinline__ void gs_phase_b(const T* tri, const T* sv, const int32_t* nodes, int cnt, int lane, const T* __restrict__ diagVal, const T* __restrict__ diagBlockInv, T* x, T* hD,
-    const T* ldsD, T* ldsX)
+    const T* ldsD)
 {
     constexpr int TRI = GsLds<T, SB>::TRI;
     const int me = lane;
@@ -335,7 +335,6 @@ __device__ __forceinline__ void gs_phase_b(const T* tri, const T* sv, const int3
 #pragma unroll
         for (int e = 0; e < 9; ++e) dd[e] = i >= 0 ? (ldsD ? ldsD[9 * me + e] : diagVal[9 * (int64_t)i + e]) : (T)0; // ldsD: staged by the caller
     }
-    if (ldsX && i >= 0) ldsX[3 * me] = h0, ldsX[3 * me + 1] = h1, ldsX[3 * me + 2] = h2; // k_gs_block2: the block's other sub-block reads these instead of global memory
     if (i >= 0) {
         if (WT) {
             __hip_atomic_store(x + 3 * (int64_t)i, h0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -356,7 +355,7 @@ __device__ __forceinline__ void gs_phase_b(const T* tri, const T* sv, const int3
 }
 
 // ---------------- the finest-level colour pass as two kernels (levels prepared by k_gs_images, mg_build.hip)
-// Measured on k_gs_block / k_gs_block2 (per-phase timestamps, C2): a colour launch lasts as long as its slowest workgroup, an interior
+// Measured on k_gs_block (per-phase timestamps, C2): a colour launch lasts as long as its slowest workgroup, an interior
 // block, which walks a ~45 us chain of dependent round trips (header -> columns -> values -> gathers -> D^-1 -> sums, twice per
 // sub-block) even when it has nothing but its in-block couplings to read (first colour), and up to 45 us more where the off-block
 // half rows are long (last colour) — while half of the workgroups (surface blocks) have long finished and HBM idles.  So:
@@ -812,10 +811,11 @@ __global__ __launch_bounds__(256) void k_gs_colour(const T* __restrict__ img, co
 // in sweep order; a workgroup of pass p
 //   1. streams the needed half of its rows into registers and files the in-sub-block couplings into the LDS triangle —
 //      none of this depends on the unknowns, so it overlaps with the substitution phase of earlier passes;
-//   2. a) makes sure everything older than pass p-1 that it reads is published and folds those columns into the staged
-//         right-hand side;  b) waits for what pass p-1 publishes (its adjacent blocks of that colour, or its own block's
-//         previous sub-block): point-to-point through gs_flag stamps, or pass counters (HOT_GS_PASS_COUNTERS);
-//   3. gathers the remaining columns, reduces the row sums, runs phase B, publishes (write-through stores, then the stamp).
+//   2. gathers every column that is older than pass p-1 (published two or more passes ago, so nearly always there) and folds
+//      those columns into the staged right-hand side, off the critical path;
+//   3. gathers the columns of pass p-1 (its adjacent blocks of that colour, or its own block's previous sub-block), reduces
+//      the row sums, runs phase B and publishes with write-through stores.
+// Hand-off: the unknowns are their own flags (ld3 in the kernel); nothing else is waited for or signalled.
 // Progress: workgroups are dispatched in index order (per XCD), so every workgroup a resident one waits for has been
 // dispatched before it and waits on nothing itself that is not; the spin is bounded anyway and reports through `err`.
 // "not written yet in this half sweep": signalling-NaN payloads that no arithmetic result carries (a computed NaN is the canonical quiet one)
@@ -854,14 +854,13 @@ __device__ unsigned long long gs_clk[34 * 8];
 // area the triangle of in-block couplings occupied (before the wait for the previous pass), every wavefront forms four rows of the product
 // (lane = column, fixed-order DPP sums) — 64 dependent broadcast-FMA steps of 150 - 190 ns become one round of ~1 us.
 // Register budget: SB = 64 runs 1024 threads, four wavefronts per SIMD, 128 registers a lane, and in fp64 the nine values of a wavefront's four rows are
-// 72 of them.  They live from the streaming (1.) to the early gathers (2a.) and no further: the slots of pass p-1 load their nine values again beside
-// the late gather (3.), a row's id and tail range sit in scalar registers (WINV) or LDS (rng), and the stamp / counter hand-offs exist in the A/B
-// build only (dflag).  Carried across both waits the values cost 55 - 66 spilled registers: 63 - 77 MB of scratch traffic per launch at C2's
-// level 1.  No instantiation has scratch (tests/test_kernel_resources.py).
+// 72 of them.  They live from the streaming (1.) to the early gathers (2.) and no further: the slots of pass p-1 load their nine values again beside
+// the late gather (3.), and a row's id and tail range sit in scalar registers (WINV) or LDS (rng).  Carried across both gathers the values cost
+// 55 - 66 spilled registers: 63 - 77 MB of scratch traffic per launch at C2's level 1.  No instantiation has scratch (tests/test_kernel_resources.py).
 template <class T, bool FWD, int SB, bool WINV = false>
 __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict__ col, const T* __restrict__ val, const uint32_t* __restrict__ ckey, const int32_t* __restrict__ gs_order,
     const int32_t* __restrict__ block_start, const T* __restrict__ diagVal, const T* __restrict__ diagBlockInv, const T* __restrict__ rhs, T* x, T* hD, GsPasses P,
-    const int32_t* __restrict__ rowcnt, int* done, int* err, const int32_t* __restrict__ nbr, int* flag, int epoch, int dataflag,
+    const int32_t* __restrict__ rowcnt, int* err /*set when a gather gave up waiting (pinned host memory, sticky)*/,
     T* unset_next /*not null: the target of the NEXT half sweep (nobody reads it during this one): every workgroup marks its rows' unknowns there "not written yet", instead of a fill launch between the sweeps*/,
     const T* __restrict__ gs_w /*WINV: [block][direction][9][TRI]*/)
 {
@@ -872,21 +871,13 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
     unsigned long long gclk_[5] = { 0, 0, 0, 0, 0 }, gt0_ = clock64();
 #endif
     constexpr int RQ = 4, NW = SB / RQ; // rows per wave, waves per workgroup (blockDim.x == 64 * NW)
-    // dataflag: the unknowns are their own flags.  The host fills x with a bit pattern no computation produces (GsUnset) before the
+    // The unknowns are their own flags.  The host fills x with a bit pattern no computation produces (GsUnset) before the
     // sweep; a reader of another block's unknown re-loads it until it is something else.  No flag array, no "data, wait for the
     // acknowledgement, flag" on the producer's side and no "flag, then data" round trip on the consumer's: a value is used the
     // moment it lands.  Every node is written exactly once per half sweep, so no stale value can be mistaken for a new one.
-    // (the inverse images run with the data-flag hand-off only, and so does everything outside the A/B build — gs_plan; chained_sweep checks it:
-    // the stamp and counter protocols then cost neither registers nor the look-up of 26 neighbours per workgroup)
-#ifdef HOT_AB_KERNELS
-    const bool dflag = WINV || dataflag != 0;
-#else
-    constexpr bool dflag = true;
-#endif
     auto ld3 = [&](int64_t j, T& x0, T& x1, T& x2) {
         x0 = __hip_atomic_load(x + 3 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), x1 = __hip_atomic_load(x + 3 * j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
         x2 = __hip_atomic_load(x + 3 * j + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!dflag) return;
         int spins = 0;
         while (GsUnset<T>::is(x0) || GsUnset<T>::is(x1) || GsUnset<T>::is(x2)) {
             __builtin_amdgcn_s_sleep(2);
@@ -1020,60 +1011,9 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
             }
         }
     }
-    // ---- 2a. every column except those of pass p-1 was published two or more passes ago: make sure pass p-2 is complete (it
-    //          nearly always is) and fold those columns into the staged right-hand side now, off the critical path
-    // point-to-point mode (nbr != null): a sub-block only waits for the adjacent blocks whose colours run
-    // earlier in the sweep, each of which stamps flag[block] with the sweep number when its nodes are published — no pass-wide
-    // counter, so a slow block holds up its neighbours only
-    // flag index = 4 * block + sub-block.  A sub-block waits for the sub-block before it in its own block, which has waited
-    // for the one before that, so a block's last sub-block in sweep order vouches for the whole block.
-    int early_idx = -1, late_idx = -1; // lanes 0..27 of wavefront 0: what to see stamped before the early / the late gather
-    if (!dflag && nbr && tid < 26) { // (data flags: nobody waits for a stamp)
-        const int nb = nbr[(int64_t)b * 26 + tid];
-        if (nb >= 0) {
-            const int cn = nb >> 28, gid = nb & 0x0fffffff;
-            int qlast = -1;
-            for (int q = 0; q < P.npass; ++q)
-                if (P.color[q] == cn) qlast = q;
-            if (qlast >= 0 && qlast < p) { // that colour runs before this one
-                if (qlast < p - 1)
-                    early_idx = 4 * gid + P.sub[qlast];
-                else {
-                    late_idx = 4 * gid + P.sub[qlast];
-                    if (qlast > 0 && P.color[qlast - 1] == cn) early_idx = 4 * gid + P.sub[qlast - 1];
-                }
-            }
-        }
-    }
-    if (!dflag && nbr && tid == 26 && p > 0 && P.color[p - 1] == P.color[p]) late_idx = 4 * b + P.sub[p - 1];
-    if (!dflag && nbr && tid == 27 && p > 1 && P.color[p - 2] == P.color[p]) early_idx = 4 * b + P.sub[p - 2];
-    auto wait_blocks = [&](int idx) { // spin until that sub-block carries the current sweep number
-        if (idx < 0) return;
-        int spins = 0;
-        while (__hip_atomic_load(flag + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1 << 22) || ((spins & 1023) == 0 && *(volatile int*)err)) {
-                *(volatile int*)err = 1;
-                break;
-            }
-        }
-    };
-    if (dflag) {
-    }
-    else if (nbr)
-        wait_blocks(early_idx);
-    else if (p > 1 && tid == 0) {
-        const int need2 = P.wg_begin[p - 1] - P.wg_begin[p - 2];
-        int spins = 0;
-        while (__hip_atomic_load(done + p - 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need2) {
-            __builtin_amdgcn_s_sleep(4);
-            if (++spins > (1 << 22) || ((spins & 1023) == 0 && *(volatile int*)err)) {
-                *(volatile int*)err = 1;
-                break;
-            }
-        }
-    }
-    __syncthreads(); // also orders the staging of D^-1 / D / rhs (and the zeroed triangle) before their users
+    // ---- 2. every column except those of pass p-1 was published two or more passes ago (nearly always; ld3 waits where one
+    //         was not): fold those columns into the staged right-hand side now, off the critical path
+    __syncthreads(); // orders the staging of D^-1 / D / rhs (and the zeroed triangle) before their users
     GS_CLK(1);
     auto is_late = [&](uint32_t keyj) { return (((keyj >> 28) << 8) | (((keyj & 127u) - 1u) / (uint32_t)SB)) == prevkey; };
     bool tail_late[RQ]; // the tail of the half row (slots past the first 64) holds columns of pass p-1 (rows are sorted to avoid it)
@@ -1124,28 +1064,9 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
         if (lane == 0) srhs[3 * ii] -= e0, srhs[3 * ii + 1] -= e1, srhs[3 * ii + 2] -= e2;
     }
     GS_CLK(2);
-    // ---- 2b. wait for the previous pass
-    if (!dflag) {
-        if (nbr)
-            wait_blocks(late_idx);
-        else if (p > 0 && tid == 0) {
-            const int need = P.wg_begin[p] - P.wg_begin[p - 1];
-            int spins = 0;
-            while (__hip_atomic_load(done + p - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                __builtin_amdgcn_s_sleep(4);
-                ++spins;
-                if ((spins & 1023) == 0 && *(volatile int*)err) break; // some workgroup already gave up: drain quickly
-                if (spins > (1 << 22)) {
-                    *(volatile int*)err = 1;
-                    break;
-                }
-            }
-        }
-        __syncthreads();
-    }
     // x of other workgroups was published with write-through stores and is read with sc1 loads below: no cache
     // maintenance (buffer_wbl2 / buffer_inv) on either side
-    // ---- 3. the columns of pass p-1 against the now final unknowns
+    // ---- 3. the columns of pass p-1: this is where a workgroup waits for the previous pass, unknown by unknown (ld3)
     const T* val_again = val;
     asm volatile("" : "+s"(val_again)); // (a pointer the compiler knows nothing about: the loads below are not merged with those of phase 1)
 #pragma unroll
@@ -1231,20 +1152,11 @@ __global__ __launch_bounds__(SB * 16) void k_gs_sweep(const int32_t* __restrict_
                 hD[3 * i] += h0, hD[3 * i + 1] += h1, hD[3 * i + 2] += h2;
         }
         GS_CLK_OUT();
-        return; // (data-flag hand-off only: the write-through stores are the publication)
+        return; // (the write-through stores are the publication)
     }
     if (w != 0) return;
     if (cnt > 0) gs_phase_b<T, FWD, SB, true>(tri, sv, nodes, cnt, lane, diagVal, diagBlockInv, x, hD, sD);
-    GS_CLK_OUT();
-    // ---- publish: the write-through stores of every lane have left the CU before lane 0 bumps the pass counter
-    if (dflag) return; // the write-through stores of phase B are the publication
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-        if (nbr)
-            __hip_atomic_store(flag + 4 * b + P.sub[p], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            __hip_atomic_fetch_add(done + p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    GS_CLK_OUT(); // (the write-through stores of phase B are the publication)
 }
 
 // h -= du in place (every entry, owned or not: what k_gs_residual<T, true> gathers)
@@ -1358,14 +1270,9 @@ GsPlan Ctx<T>::gs_plan(const Level<T>& L) const
     else
         p.path = simple_gs ? GsPlan::SIMPLE : GsPlan::PER_COLOUR;
     if (chained) {
-        // hand-off between passes: the unknowns are their own flags (A/B switches: HOT_GS_BLOCK_FLAGS = per-block sweep stamps,
-        // HOT_GS_PASS_COUNTERS = one counter per pass instead of point-to-point block flags)
-        const bool pass_counters = ab_flag("HOT_GS_PASS_COUNTERS");
-        p.p2p = !pass_counters;
-        p.dataflag = !pass_counters && !ab_flag("HOT_GS_BLOCK_FLAGS");
         // whole-block passes on the precomputed inverses of the in-block triangles (A/B build: HOT_GS_NO_WINV = the 64-step substitution)
-        p.winv = p.sb == 64 && L.gs_w_ready && p.dataflag && !ab_flag("HOT_GS_NO_WINV");
-        p.marks = p.dataflag && L.tmp.p;
+        p.winv = p.sb == 64 && L.gs_w_ready && !ab_flag("HOT_GS_NO_WINV");
+        p.marks = L.tmp.p != nullptr;
     }
     return p;
 }
@@ -1637,7 +1544,7 @@ void Ctx<T>::gs_smooth_dev(int level, int iterations, T* u, T* r, T* du, T* dAu,
         }
     };
 
-    // ---- CHAINED: one k_gs_sweep launch per half sweep, its passes handed off inside (plan.dataflag / plan.p2p)
+    // ---- CHAINED: one k_gs_sweep launch per half sweep, its passes handed off inside through the unknowns
     if (tmp_marked && !plan.marks) zero(n3, hdu), tmp_marked = false; // (cannot happen: gs_marks_wanted takes the same decision)
     GsPasses PF{}, PB{};
     if (plan.path == GsPlan::CHAINED) {
@@ -1651,7 +1558,6 @@ void Ctx<T>::gs_smooth_dev(int level, int iterations, T* u, T* r, T* du, T* dAu,
             for (int h = 0; h < nsub; ++h) add(PF, c, h);
         for (int c = 7; c >= 0; --c)
             for (int h = nsub - 1; h >= 0; --h) add(PB, c, h);
-        gs_done.reserve(64);
     }
     bool du_marked = false;
     auto chained_sweep = [&](bool fwd) {
@@ -1666,24 +1572,13 @@ void Ctx<T>::gs_smooth_dev(int level, int iterations, T* u, T* r, T* du, T* dAu,
         // (restrict_dev / the k_apmv_sub of the way up: unset_level), the backward target by the forward sweep itself; a fill launch otherwise
         const bool marked = fwd ? tmp_marked : du_marked;
         if (fwd) tmp_marked = false;
-        if (plan.dataflag && !marked)
-            HOT_LAUNCH(this, "gs_fill_unset", k_gs_fill_unset<T>, div_up(n3, 256), 256, 0, n3, xx);
-        else if (plan.dataflag)
-            ;
-        else if (plan.p2p)
-            ++gs_epoch;
-        else
-            HOT_HIP(hipMemsetAsync(gs_done.p, 0, 40 * sizeof(int), stream));
+        if (!marked) HOT_LAUNCH(this, "gs_fill_unset", k_gs_fill_unset<T>, div_up(n3, 256), 256, 0, n3, xx);
         const int grid = P.wg_begin[P.npass];
-        const int dataflag = plan.dataflag ? 1 : 0;
-#ifndef HOT_AB_KERNELS
-        HOT_CHECK(dataflag, HOT_ERR_INVALID, "k_gs_sweep: only the A/B build carries the stamp and pass-counter hand-offs");
-#endif
 #define HOT_GS_CASE(F, S, ...)                                                                                                                                         \
     HOT_LAUNCH(this, lname(nm, L.id).c_str(), (k_gs_sweep<T, F, S, ##__VA_ARGS__>), grid, 16 * S, (GsLds<T, S>::bytes + 21 * S * sizeof(T) + 128), L.col.p, L.val.p, L.ckey.p, L.gs_order.p, L.gs_block_start.p, \
-        L.diagVal.p, L.diagBlockInv.p, rhs, xx, hD, P, rc, gs_done.p, (int*)(hscal + 250), plan.p2p ? L.gs_nbr.p : (const int32_t*)nullptr, L.gs_flag.p, gs_epoch, dataflag, \
-        (fwd && dataflag) ? du : (T*)nullptr, L.gs_w.p)
-        du_marked = fwd && dataflag;
+        L.diagVal.p, L.diagBlockInv.p, rhs, xx, hD, P, rc, (int*)(hscal + 250), \
+        fwd ? du : (T*)nullptr, L.gs_w.p)
+        du_marked = fwd;
         if (plan.winv) {
             if (fwd)
                 HOT_GS_CASE(true, 64, true);

@@ -47,7 +47,7 @@ struct Rccl {
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr;
     int rank = 0, size = 1;
-    bool self_via_p2p = false; // self-test: a rank's message to itself goes through the grouped ncclSend / ncclRecv as well
+    bool self_via_group = false; // self-test: a rank's message to itself goes through the grouped ncclSend / ncclRecv as well
     char* scratch = nullptr; // device staging of host payloads (scalars, counts)
     size_t scratch_bytes = 0;
     char* stage(size_t bytes)
@@ -94,11 +94,11 @@ int32_t cb_alltoallv(void* user, const void* send, const int64_t* soff, const in
     Rccl* r = (Rccl*)user;
     if (!on_device) return 1; // the library only exchanges device payloads this way
     bool ok = true;
-    if (sbytes[r->rank] > 0 && !r->self_via_p2p) // a rank's message to itself (the library sends none today; the contract allows it)
+    if (sbytes[r->rank] > 0 && !r->self_via_group) // a rank's message to itself (the library sends none today; the contract allows it)
         ok = hipMemcpyAsync((char*)recv + roff[r->rank], (const char*)send + soff[r->rank], (size_t)sbytes[r->rank], hipMemcpyDeviceToDevice, r->stream) == hipSuccess;
     if (!ok || api().GroupStart() != ncclSuccess) return 1; // no GroupEnd without a GroupStart
     for (int p = 0; p < r->size && ok; ++p) {
-        if (p == r->rank && !r->self_via_p2p) continue; // (self_via_p2p, self-test only: the message to itself takes the grouped Send / Recv like a peer's)
+        if (p == r->rank && !r->self_via_group) continue; // (self_via_group, self-test only: the message to itself takes the grouped Send / Recv like a peer's)
         if (rbytes[p] > 0) ok = ok && api().Recv((char*)recv + roff[p], (size_t)rbytes[p], ncclChar, p, r->comm, r->stream) == ncclSuccess;
         if (sbytes[p] > 0) ok = ok && api().Send((const char*)send + soff[p], (size_t)sbytes[p], ncclChar, p, r->comm, r->stream) == ncclSuccess;
     }
@@ -236,14 +236,14 @@ int hot_rccl_selftest(hot_ctx* ctx)
     double *xs = nullptr, *xr = nullptr;
     ok = ok && hipMalloc((void**)&xs, stot * sizeof(double)) == hipSuccess && hipMalloc((void**)&xr, rtot * sizeof(double)) == hipSuccess;
     for (int pass = 0; pass < 2 && ok; ++pass) {
-        r->self_via_p2p = pass == 1;
+        r->self_via_group = pass == 1;
         ok = hipMemcpyAsync(xs, hsend.data(), stot * sizeof(double), hipMemcpyHostToDevice, r->stream) == hipSuccess && hipMemsetAsync(xr, 0xff, rtot * sizeof(double), r->stream) == hipSuccess;
         ok = ok && cb_alltoallv(r, xs, so.data(), sb.data(), xr, ro.data(), rb.data(), 1) == 0;
         ok = ok && hipMemcpyAsync(hrecv.data(), xr, rtot * sizeof(double), hipMemcpyDeviceToHost, r->stream) == hipSuccess && hipStreamSynchronize(r->stream) == hipSuccess;
         for (int p = 0; p < r->size && ok; ++p)
             for (int64_t k = 0; k < len(p, r->rank) && ok; ++k) ok = hrecv[ro[p] / 8 + k] == 1e6 * p + 1e3 * r->rank + (double)k;
     }
-    r->self_via_p2p = false;
+    r->self_via_group = false;
     if (xs) (void)hipFree(xs);
     if (xr) (void)hipFree(xr);
     (void)hipFree(d), (void)hipFree(g);

@@ -1,5 +1,5 @@
 """The library picks kernel variants by problem size (block GS: one launch per colour on large levels, one chained launch
-per half sweep with point-to-point block flags on small ones; sub-block size 32 / 64); hot_config.gs_chain / gs_sub_block
+per half sweep, its passes handed off through the unknowns themselves, on small ones; sub-block size 32 / 64); hot_config.gs_chain / gs_sub_block
 override the choice.  The parity tests use small problems, so without this file only the small-problem variants would be
 compared with the oracle.  First-generation kernels and launch-structure alternatives live only in the A/B build of the
 library (libhotmi355x_ab.so, -DHOT_AB_KERNELS), where environment variables select them.  Each case re-runs the relevant
@@ -22,10 +22,6 @@ CASES = [
     ({"HOT_TEST_CFG": "gs_chain=2,gs_sub_block=16"}, SOLVER, "smoothers or vcycle"),
     ({"HOT_GS_NO_WINV": "1"}, SOLVER, "smoothers or vcycle or iterates"),  # chained whole-block passes with the 64-step substitution instead of the product with the blocks' inverse images (k_gs_winv)
     ({"HOT_TEST_CFG": "gs_chain=2", "HOT_GS_NO_WINV": "1"}, SOLVER, "smoothers or vcycle"),
-    ({"HOT_GS_PASS_COUNTERS": "1"}, SOLVER, "smoothers or vcycle or iterates"),
-    ({"HOT_TEST_CFG": "gs_chain=2,gs_sub_block=32", "HOT_GS_PASS_COUNTERS": "1"}, SOLVER, "smoothers or vcycle"),
-    ({"HOT_TEST_CFG": "gs_chain=2,gs_sub_block=32", "HOT_GS_BLOCK_FLAGS": "1"}, SOLVER, "smoothers or vcycle or iterates"),  # hand-off through per-block sweep stamps
-    ({"HOT_GS_BLOCK_FLAGS": "1"}, SOLVER, "smoothers or vcycle"),
     ({"HOT_TEST_CFG": "gs_chain=1,gs_sub_block=32", "HOT_GS_PAIR": "1"}, SOLVER, "smoothers or vcycle or iterates"),  # round 4 / 5: the colour pass as the kernel pair k_gs_offblock + k_gs_subst (what a row-partitioned level runs) instead of the one launch k_gs_colour
     ({"HOT_TEST_CFG": "gs_chain=1,gs_sub_block=32", "HOT_GS_PAIR": "1", "HOT_GS_OFF_WAVES": "64"}, SOLVER, "smoothers or vcycle"),
     ({"HOT_TEST_CFG": "gs_chain=1,gs_sub_block=32", "HOT_GS_SUBST_D": "4"}, SOLVER, "smoothers or vcycle"),  # image columns in flight per substitution wavefront

@@ -38,6 +38,14 @@ STICKY, SLIP, SEPARATE = 1, 2, 3
 HALFSPACE, SPHERE, BOX, CAPPED_CYLINDER, TORUS, ROTATED_BOX, UNION, DIFFERENCE = 0, 1, 2, 3, 4, 5, 6, 7
 
 
+class hot_plasticity_class(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("yield_stress", C.c_double), ("snow", C.c_double * 5)]
+
+
+NONE, VON_MISES, SNOW = 0, 1, 2  # hot_plasticity_class.kind
+MAX_PLASTICITY_CLASSES = 16
+
+
 class hot_stats(C.Structure):
     _fields_ = [
         ("iterations", C.c_int32), ("converged", C.c_int32), ("linesearch_trials", C.c_int32),
@@ -64,7 +72,8 @@ ABI_VERSION = 7  # include/hot_mi355x.h HOT_ABI_VERSION: the layout of hot_confi
 
 
 # declared by the header for the HIP product only (device-runtime services a host-memory implementation of the ABI has no use for)
-PRODUCT_ONLY_SYMBOLS = ["rccl_unique_id", "rccl_attach", "rccl_selftest", "get_level_inblock_nnzb", "copy_bandwidth"]
+PRODUCT_ONLY_SYMBOLS = ["rccl_unique_id", "rccl_attach", "rccl_selftest", "get_level_inblock_nnzb", "copy_bandwidth",
+                        "set_plasticity_classes", "get_plasticity_classes", "plasticity_eval_classes"]
 
 
 class HotError(RuntimeError):
@@ -563,6 +572,58 @@ class Context:
         lam = np.array(np.broadcast_to(lam, (n,)), self.T)
         Jp = np.ones(n, self.T) if Jp is None else np.array(Jp, self.T)
         self._call("plasticity_eval", C.c_int32(kind), C.c_int32(n), _ptr(F), _ptr(mu), _ptr(lam), _ptr(Jp))
+        return F, mu, lam, Jp
+
+    # ---- per-particle plasticity classes (HIP product only; bound on first use)
+    def _product_fn(self, name, argtypes):
+        f = getattr(self.lib.lib, self.lib.prefix + name)
+        f.restype, f.argtypes = C.c_int, argtypes
+        return f
+
+    def _product_call(self, name, argtypes, *args):
+        rc = self._product_fn(name, argtypes)(self.h, *args)
+        if rc != 0:
+            msg = self.lib.fn["last_error"](self.h)
+            raise HotError(f"{self.lib.prefix}{name} -> {rc}: {msg.decode() if msg else ''}")
+
+    def set_plasticity_classes(self, classes, particle_class=None):
+        """Install a table of up to 16 plasticity classes — dicts(kind=0 none / 1 von Mises / 2 snow, yield_stress=.., snow=(psi, theta_c, theta_s, min_Jp,
+        max_Jp)) — and one class index per particle (order of set_particles / get_particles); g2p then applies every particle's own return mapping and
+        ignores cfg.plasticity.  particle_class=None keeps the classes the context holds (after read_restart); an empty table removes it."""
+        arr = (hot_plasticity_class * max(len(classes), 1))()
+        for o, d in zip(arr, classes):
+            o.kind, o.yield_stress = int(d.get("kind", 0)), float(d.get("yield_stress", 0.0))
+            for k, v in enumerate(d.get("snow", (0.0,) * 5)):
+                o.snow[k] = float(v)
+        pc = None
+        if particle_class is not None:
+            pc = np.ascontiguousarray(particle_class, np.int32)
+            if pc.shape != (self.counts()["Np"],):
+                raise HotError(f"set_plasticity_classes: particle_class has shape {pc.shape}, the context holds {self.counts()['Np']} particles")
+        self._product_call("set_plasticity_classes", [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p], C.c_int32(len(classes)), C.cast(arr, C.c_void_p), _ptr(pc))
+
+    def plasticity_classes(self):
+        """(classes, particle_class): the installed table as a list of dicts and the particles' classes in get_particles order (None while the context holds none)."""
+        n = C.c_int32()
+        arr = (hot_plasticity_class * MAX_PLASTICITY_CLASSES)()
+        sig = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+        self._product_call("get_plasticity_classes", sig, C.byref(n), C.cast(arr, C.c_void_p), None)
+        classes = [dict(kind=o.kind, yield_stress=o.yield_stress, snow=tuple(o.snow)) for o in arr[:n.value]]
+        if n.value == 0:
+            return classes, None
+        pc = np.empty(self.counts()["Np"], np.int32)
+        self._product_call("get_plasticity_classes", sig, C.byref(n), None, _ptr(pc))
+        return classes, pc
+
+    def plasticity_eval_classes(self, F, mu, lam, Jp, cls):
+        """The installed class table applied to samples (class cls[i] to sample i) through the device functions g2p uses, on copies: (F, mu, lam, Jp)."""
+        F = np.array(F, self.T, order="C").reshape(-1, 9)
+        n = F.shape[0]
+        mu = np.array(np.broadcast_to(mu, (n,)), self.T)
+        lam = np.array(np.broadcast_to(lam, (n,)), self.T)
+        Jp = np.ones(n, self.T) if Jp is None else np.array(np.broadcast_to(Jp, (n,)), self.T)
+        cls = np.ascontiguousarray(np.broadcast_to(cls, (n,)), np.int32)
+        self._product_call("plasticity_eval_classes", [C.c_void_p, C.c_int32] + [C.c_void_p] * 5, C.c_int32(n), _ptr(F), _ptr(mu), _ptr(lam), _ptr(Jp), _ptr(cls))
         return F, mu, lam, Jp
 
     def advance(self, dt):

@@ -424,6 +424,24 @@ int hot_plasticity_eval(hot_ctx* ctx, int32_t kind, int32_t n, void* F, void* mu
     ctx->impl->plasticity_eval(kind, n, F, mu, lambda, Jp);
     HOT_API_END
 }
+int hot_set_plasticity_classes(hot_ctx* ctx, int32_t n, const hot_plasticity_class* classes, const int32_t* particle_class)
+{
+    HOT_API_BEGIN
+    ctx->impl->set_plasticity_classes(n, classes, particle_class);
+    HOT_API_END
+}
+int hot_get_plasticity_classes(hot_ctx* ctx, int32_t* n, hot_plasticity_class* classes, int32_t* particle_class)
+{
+    HOT_API_BEGIN
+    ctx->impl->get_plasticity_classes(n, classes, particle_class);
+    HOT_API_END
+}
+int hot_plasticity_eval_classes(hot_ctx* ctx, int32_t n, void* F, void* mu, void* lambda, void* Jp, const int32_t* cls)
+{
+    HOT_API_BEGIN
+    ctx->impl->plasticity_eval_classes(n, F, mu, lambda, Jp, cls);
+    HOT_API_END
+}
 int hot_advance(hot_ctx* ctx, double dt, hot_stats* stats)
 {
     HOT_API_BEGIN

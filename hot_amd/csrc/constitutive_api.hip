@@ -72,6 +72,23 @@ __global__ __launch_bounds__(256) void k_plasticity_eval(int kind, int n, T* __r
     for (int c = 0; c < 9; ++c) F[9 * (int64_t)p + c] = Fc.a[c];
 }
 
+// the installed class table on caller-supplied samples: the device function k_g2p<T, 3> calls (cls_tab: the context's table; cls: the sample's class)
+template <class T>
+__global__ __launch_bounds__(256) void k_plasticity_eval_classes(int n, T* __restrict__ F, T* Mu, T* Lam, T* Jp, const int32_t* __restrict__ cls, const T* __restrict__ cls_tab)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    Mat3<T> Fc;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Fc.a[c] = F[9 * (int64_t)p + c];
+    T mu = 0, la = 0, jp = 0;
+    bool hardened;
+    plasticity_classes_project(Fc, cls_tab + PCLS_STRIDE * cls[p], Mu, Lam, Jp, (int64_t)p, mu, la, jp, hardened);
+    if (hardened) Mu[p] = mu, Lam[p] = la, Jp[p] = jp;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) F[9 * (int64_t)p + c] = Fc.a[c];
+}
+
 template <class T>
 void Ctx<T>::constitutive_eval(int32_t n, const void* F, const void* mu, const void* lambda, int32_t project, void* psi, void* P, void* dPdF)
 {
@@ -103,6 +120,28 @@ void Ctx<T>::plasticity_eval(int32_t kind, int32_t n, void* F, void* mu, void* l
         (T)cfg.snow[3], (T)cfg.snow[4]);
     download(F, dF.p, 9 * (size_t)n), download(mu, dMu.p, n), download(lambda, dLam.p, n);
     if (kind == 2) download(Jp, dJp.p, n);
+    sync();
+}
+
+template <class T>
+void Ctx<T>::plasticity_eval_classes(int32_t n, void* F, void* mu, void* lambda, void* Jp, const int32_t* cls)
+{
+    need(ncls > 0, "hot_plasticity_eval_classes: no class table is installed (hot_set_plasticity_classes)");
+    need(n > 0 && F && mu && lambda && Jp && cls, "hot_plasticity_eval_classes: F, mu, lambda, Jp and cls are required");
+    std::vector<int32_t> hc((size_t)n);
+    HOT_HIP(hipMemcpyAsync(hc.data(), cls, (size_t)n * sizeof(int32_t), hipMemcpyDefault, stream));
+    sync();
+    for (int32_t c : hc) need(c >= 0 && c < ncls, "hot_plasticity_eval_classes: a sample's class lies outside the installed table");
+    DBuf<T> dF, dMu, dLam, dJp;
+    DBuf<int32_t> dCls;
+    dF.reserve(9 * (size_t)n), dMu.reserve(n), dLam.reserve(n), dJp.reserve(n), dCls.reserve(n);
+    HOT_HIP(hipMemcpyAsync(dF.p, F, 9 * (size_t)n * sizeof(T), hipMemcpyDefault, stream));
+    HOT_HIP(hipMemcpyAsync(dMu.p, mu, (size_t)n * sizeof(T), hipMemcpyDefault, stream));
+    HOT_HIP(hipMemcpyAsync(dLam.p, lambda, (size_t)n * sizeof(T), hipMemcpyDefault, stream));
+    HOT_HIP(hipMemcpyAsync(dJp.p, Jp, (size_t)n * sizeof(T), hipMemcpyDefault, stream));
+    HOT_HIP(hipMemcpyAsync(dCls.p, hc.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HOT_LAUNCH(this, "plasticity_eval_classes", k_plasticity_eval_classes<T>, div_up(n, 256), 256, 0, n, dF.p, dMu.p, dLam.p, dJp.p, dCls.p, clsTab.p);
+    download(F, dF.p, 9 * (size_t)n), download(mu, dMu.p, n), download(lambda, dLam.p, n), download(Jp, dJp.p, n);
     sync();
 }
 

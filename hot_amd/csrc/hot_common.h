@@ -13,6 +13,10 @@
 
 namespace hot {
 
+// Per-particle plasticity classes (hot_set_plasticity_classes): at most PCLS_MAX classes; on the device a class is PCLS_STRIDE scalars of the context's
+// table: kind (0 none, 1 von Mises, 2 snow), yield stress, snow psi / theta_c / theta_s / min_Jp / max_Jp, one pad.
+constexpr int PCLS_MAX = 16, PCLS_STRIDE = 8;
+
 struct Error {
     int code;
     std::string msg;

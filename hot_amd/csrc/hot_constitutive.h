@@ -6,6 +6,7 @@
 //                        (SvdBasedIsotropicHelper.h:223-247) — the 9x9 dP/dF of CorotatedIsotropic.h:174-230 is
 //                        never materialised as a 25-term sum per entry; callers contract U K V^T directly.
 //   von_mises_project / snow_project   PlasticityApplier.cpp:96-131 / :18-50
+//   plasticity_classes_project         both, chosen per particle by its class (PlasticityApplier.h:36-53: an applier belongs to a particle handle)
 #pragma once
 #include "hot_svd.h"
 
@@ -180,12 +181,12 @@ __device__ __forceinline__ Mat3<T> hess_apply(const HessBlocks<T>& h, const Mat3
     return m3_mul_bt(m3_mul(h.U, K), h.V);
 }
 
+// The return mappings on the singular values alone, after the SVD: the arithmetic von_mises_project / snow_project (k_g2p<T, 1 / 2>,
+// k_plasticity_eval) and the per-particle class paths (plasticity_classes_project: k_g2p<T, 3>, k_plasticity_eval_classes) share.
+// von Mises radial return (PlasticityApplier.cpp:96-131): false = inside the yield surface, the caller leaves the strain as it is
 template <class T>
-__device__ inline bool von_mises_project(Mat3<T>& strain, T mu, T lambda, T yield_stress)
+__device__ __forceinline__ bool von_mises_return(T (&s)[3], T mu, T lambda, T yield_stress)
 {
-    Mat3<T> U, V;
-    T s[3];
-    svd3(strain, U, s, V);
 #pragma unroll
     for (int d = 0; d < 3; ++d) s[d] = s[d] > (T)1e-4 ? s[d] : (T)1e-4;
     T J = s[0] * s[1] * s[2];
@@ -198,19 +199,34 @@ __device__ inline bool von_mises_project(Mat3<T>& strain, T mu, T lambda, T yiel
     T scaled_tauy = hsqrt((T)2 / (T)3) * yield_stress;
     if (s_norm - scaled_tauy <= (T)0) return false;
     T alpha = scaled_tauy / s_norm;
-    T sn[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         T tau_new = alpha * st[d] + tr / (T)3;
         T b2m4ac = mu * mu - (T)2 * mu * (lambda * (J - (T)1) * J - tau_new);
-        sn[d] = (mu + hsqrt(b2m4ac)) / ((T)2 * mu);
+        s[d] = (mu + hsqrt(b2m4ac)) / ((T)2 * mu);
     }
+    return true;
+}
+// U diag(s) V^T
+template <class T>
+__device__ __forceinline__ Mat3<T> m3_usvt(const Mat3<T>& U, const T (&s)[3], const Mat3<T>& V)
+{
     Mat3<T> US;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int r = 0; r < 3; ++r) US(r, c) = U(r, c) * sn[c];
-    strain = m3_mul_bt(US, V);
+        for (int r = 0; r < 3; ++r) US(r, c) = U(r, c) * s[c];
+    return m3_mul_bt(US, V);
+}
+
+template <class T>
+__device__ inline bool von_mises_project(Mat3<T>& strain, T mu, T lambda, T yield_stress)
+{
+    Mat3<T> U, V;
+    T s[3];
+    svd3(strain, U, s, V);
+    if (!von_mises_return(s, mu, lambda, yield_stress)) return false;
+    strain = m3_usvt(U, s, V);
     return true;
 }
 
@@ -221,12 +237,10 @@ __device__ __forceinline__ float hexp<float>(float x) { return expf(x); }
 template <>
 __device__ __forceinline__ double hexp<double>(double x) { return exp(x); }
 
+// snow (PlasticityApplier.cpp:18-50): the clamp of the singular values, Jp and the hardening of mu / lambda; det_strain = det of the trial strain
 template <class T>
-__device__ inline void snow_project(Mat3<T>& strain, T& mu, T& lambda, T& Jp, T psi, T theta_c, T theta_s, T min_Jp, T max_Jp)
+__device__ __forceinline__ void snow_return(T (&s)[3], T det_strain, T& mu, T& lambda, T& Jp, T psi, T theta_c, T theta_s, T min_Jp, T max_Jp)
 {
-    Mat3<T> U, V;
-    T s[3];
-    svd3(strain, U, s, V);
     T Fe_det = (T)1;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -234,19 +248,56 @@ __device__ inline void snow_project(Mat3<T>& strain, T& mu, T& lambda, T& Jp, T 
         s[i] = v > (T)1 - theta_c ? v : (T)1 - theta_c;
         Fe_det *= s[i];
     }
-    Mat3<T> US;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r) US(r, c) = U(r, c) * s[c];
-    T Jp_new = Jp * m3_det(strain) / Fe_det;
+    T Jp_new = Jp * det_strain / Fe_det;
     if (!(Jp_new <= max_Jp)) Jp_new = max_Jp;
     if (!(Jp_new >= min_Jp)) Jp_new = min_Jp;
-    strain = m3_mul_bt(US, V);
     T hard = hexp(psi * (Jp - Jp_new));
     mu *= hard;
     lambda *= hard;
     Jp = Jp_new;
+}
+
+template <class T>
+__device__ inline void snow_project(Mat3<T>& strain, T& mu, T& lambda, T& Jp, T psi, T theta_c, T theta_s, T min_Jp, T max_Jp)
+{
+    Mat3<T> U, V;
+    T s[3];
+    svd3(strain, U, s, V);
+    snow_return(s, m3_det(strain), mu, lambda, Jp, psi, theta_c, theta_s, min_Jp, max_Jp);
+    strain = m3_usvt(U, s, V);
+}
+
+// Per-particle plasticity classes (hot_set_plasticity_classes): `par` = the PCLS_STRIDE scalars of the lane's class in the context's table (hot_common.h).
+// The return mapping of this lane's class `par`, both mappings off ONE svd3: a wavefront without a plastic lane returns before the SVD, and each
+// singular-value update sits under a wave-uniform guard, so a wavefront of one kind (particles are sorted by cell: most of them) executes that branch
+// alone.  mu, lambda and Jp are read from the particle arrays by the lanes that need them; `hardened` tells the caller that they changed (kind 2 only).
+template <class T>
+__device__ __forceinline__ void plasticity_classes_project(Mat3<T>& strain, const T* par, const T* Mu, const T* Lam, const T* Jp_in, int64_t p, T& mu,
+    T& lambda, T& Jp, bool& hardened)
+{
+    const int kind = (int)par[0];
+    hardened = false;
+    const unsigned long long any_vm = __ballot(kind == 1), any_snow = __ballot(kind == 2);
+    if (!(any_vm | any_snow)) return;
+    Mat3<T> U, V;
+    T s[3];
+    svd3(strain, U, s, V);
+    bool changed = false;
+    if (any_vm) {
+        if (kind == 1) {
+            mu = Mu[p], lambda = Lam[p];
+            changed = von_mises_return(s, mu, lambda, par[1]);
+        }
+    }
+    if (any_snow) {
+        if (kind == 2) {
+            mu = Mu[p], lambda = Lam[p], Jp = Jp_in[p];
+            snow_return(s, m3_det(strain), mu, lambda, Jp, par[2], par[3], par[4], par[5], par[6]);
+            changed = hardened = true;
+        }
+    }
+    const Mat3<T> Fp = m3_usvt(U, s, V); // formed once, whatever the lanes' kinds
+    if (changed) strain = Fp;
 }
 
 } // namespace hot

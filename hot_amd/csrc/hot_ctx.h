@@ -119,6 +119,9 @@ struct CtxBase {
     virtual void compute_step_api(const void* residual, void* step) = 0;
     virtual void constitutive_eval(int32_t n, const void* F, const void* mu, const void* lambda, int32_t project, void* psi, void* P, void* dPdF) = 0;
     virtual void plasticity_eval(int32_t kind, int32_t n, void* F, void* mu, void* lambda, void* Jp) = 0;
+    virtual void set_plasticity_classes(int32_t n, const hot_plasticity_class* classes, const int32_t* particle_class) = 0;
+    virtual void get_plasticity_classes(int32_t* n, hot_plasticity_class* classes, int32_t* particle_class) = 0;
+    virtual void plasticity_eval_classes(int32_t n, void* F, void* mu, void* lambda, void* Jp, const int32_t* cls) = 0;
     virtual void advance(double dt, hot_stats* st) = 0;
     virtual void calculate_dt(double max_dt, double* dt, double* max_speed, double* min_corner, double* max_corner) = 0;
     virtual void advance_frame(double frame_dt, double min_dt, double max_dt, int32_t* substeps, int32_t* iterations_total, hot_stats* st) = 0;

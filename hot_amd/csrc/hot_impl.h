@@ -164,6 +164,14 @@ struct Ctx : CtxBase {
     DBuf<T> pX, pV, pM, pC, pF, pVol, pMu, pLam, pJp, pFn, pFt, pStress, pGradV;
     DBuf<int32_t> slot2orig;
     DBuf<int32_t> pGid; // global particle id (sort-key tie break of a sharded run, travels with a migrating particle)
+    // ---- per-particle plasticity classes (hot_set_plasticity_classes)
+    DBuf<int32_t> pCls; // class of every particle, sorted order like every other attribute; allocated while the context holds classes
+    bool have_cls = false; // pCls is valid: a table is installed, or hot_read_restart found the column and the table is still to come
+    int ncls = 0; // classes of the installed table; 0: none, hot_g2p follows cfg.plasticity
+    hot_plasticity_class cls_host[16] = {};
+    DBuf<T> clsTab; // the table as k_g2p<T, 3> reads it: 16 x 8 scalars {kind, yield stress, snow[5], pad}
+    void clear_plasticity_classes() { have_cls = false, ncls = 0; }
+    int32_t max_particle_class(int32_t* min_out); // one small reduction over pCls (syncs)
     void reserve_particles(int64_t n);
     void migrate_particles(); // sharded: hand every particle to the rank of its SPGrid page range (shard.hip)
     void set_particle_ids(const int32_t* ids) override;
@@ -546,6 +554,9 @@ struct Ctx : CtxBase {
     void g2p(double dt, int32_t* flags) override;
     void constitutive_eval(int32_t n, const void* F, const void* mu, const void* lambda, int32_t project, void* psi, void* P, void* dPdF) override;
     void plasticity_eval(int32_t kind, int32_t n, void* F, void* mu, void* lambda, void* Jp) override;
+    void set_plasticity_classes(int32_t n, const hot_plasticity_class* classes, const int32_t* particle_class) override;
+    void get_plasticity_classes(int32_t* n, hot_plasticity_class* classes, int32_t* particle_class) override;
+    void plasticity_eval_classes(int32_t n, void* F, void* mu, void* lambda, void* Jp, const int32_t* cls) override;
     void advance(double dt, hot_stats* st) override;
     void calculate_dt(double max_dt, double* dt, double* max_speed, double* min_corner, double* max_corner) override;
     void advance_frame(double frame_dt, double min_dt, double max_dt, int32_t* substeps, int32_t* iterations_total, hot_stats* st) override;

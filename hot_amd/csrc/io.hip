@@ -102,9 +102,15 @@ void Ctx<T>::write_restart(const char* path)
     std::ofstream o(path, std::ios::binary);
     HOT_CHECK(o.good(), HOT_ERR_INVALID, std::string("hot_write_restart: cannot open ") + path);
     put<int32_t>(o, (int32_t)Np); // DataManager::count
-    put<uint64_t>(o, 9); // number of arrays
+    put<uint64_t>(o, have_cls ? 10 : 9); // number of arrays
     put_array(o, "m", m, 1, Np), put_array(o, "P", X, 3, Np), put_array(o, "V", V, 3, Np), put_array(o, "C", C, 9, Np), put_array(o, "F", F, 9, Np);
     put_array(o, "element measure", vol, 1, Np), put_array(o, "mu", mu, 1, Np), put_array(o, "lambda", la, 1, Np), put_array(o, "Jp", jp, 1, Np);
+    if (have_cls) { // the particles' plasticity classes (the parameter table is not particle data: the caller installs it again after hot_read_restart)
+        std::vector<int32_t> ci(n);
+        get_plasticity_classes(nullptr, nullptr, ci.data());
+        std::vector<T> cl(ci.begin(), ci.end());
+        put_array(o, "plasticity class", cl, 1, Np);
+    }
     HOT_CHECK(o.good(), HOT_ERR_INVALID, "hot_write_restart: write failed");
 }
 
@@ -139,6 +145,21 @@ void Ctx<T>::read_restart(const char* path)
         HOT_CHECK((int64_t)col[kw.first].size() == count * kw.second, HOT_ERR_INVALID, std::string("hot_read_restart: array has the wrong width: ") + kw.first);
     }
     set_particles(count, col["P"].data(), col["V"].data(), col["m"].data(), col["C"].data(), col["F"].data(), col["element measure"].data(), col["mu"].data(), col["lambda"].data(), col["Jp"].data());
+    // (hot_set_particles cleared the classes.)  With a class column the context holds the classes again; hot_set_plasticity_classes with particle_class = NULL installs their table
+    if (col.count("plasticity class")) {
+        const std::vector<T>& cl = col["plasticity class"];
+        HOT_CHECK((int64_t)cl.size() == count, HOT_ERR_INVALID, "hot_read_restart: array has the wrong width: plasticity class");
+        std::vector<int32_t> ci(cl.size());
+        for (size_t p = 0; p < cl.size(); ++p) {
+            HOT_CHECK(cl[p] >= (T)0 && cl[p] < (T)PCLS_MAX && cl[p] == (T)(int32_t)cl[p], HOT_ERR_INVALID, "hot_read_restart: a plasticity class is not an integer in [0, 16)");
+            ci[p] = (int32_t)cl[p];
+        }
+        // hot_set_particles left the particles in the caller's order (slot2orig = identity)
+        pCls.reserve(pGid.cap);
+        HOT_HIP(hipMemcpyAsync(pCls.p, ci.data(), ci.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        sync();
+        have_cls = true;
+    }
 }
 
 template struct Ctx<float>;

@@ -679,7 +679,7 @@ __global__ void k_rank_of(const uint32_t* __restrict__ sorted_slot, int32_t* __r
 // Every hot_sort of a sharded context first re-shards the particles: rank r gets the r-th of `size` nearly equal runs of
 // the SPGrid page order (splitters = quantiles of a strided sample of all ranks' page ids, whole pages only), so a shard stays
 // spatially compact however the body moves, the ranks' group lists stay contiguous ranges of the global sort, and the rows a
-// rank's particles touch stay (mostly) the rows it owns.  Particles travel as records of their 29 scalars + their global id.
+// rank's particles touch stay (mostly) the rows it owns.  Particles travel as records of their 29 scalars + their global id (+ their plasticity class where the context holds classes).
 template <class T>
 void Ctx<T>::migrate_particles()
 {
@@ -765,7 +765,8 @@ void Ctx<T>::migrate_particles()
     DBuf<T> sendT, recvT;
     DBuf<int32_t> sendI, recvI;
     sendT.reserve((size_t)std::max<int64_t>(n, 1) * NC), recvT.reserve((size_t)std::max<int64_t>(incoming, 1) * NC);
-    sendI.reserve(std::max<int64_t>(n, 1)), recvI.reserve(std::max<int64_t>(incoming, 1));
+    const int NI = have_cls ? 2 : 1; // integer columns: the global id, and the plasticity class where the context holds classes (every rank does, or none)
+    sendI.reserve((size_t)std::max<int64_t>(n, 1) * NI), recvI.reserve((size_t)std::max<int64_t>(incoming, 1) * NI);
     struct Attr {
         DBuf<T>* a;
         int comps;
@@ -776,7 +777,8 @@ void Ctx<T>::migrate_particles()
             HOT_LAUNCH(this, "migrate_pack", k_pack_attr<T>, div_up((size_t)n * at.comps, 256), 256, 0, at.a->p, n, at.comps, lists.p, n, sendT.p, NC, col);
             col += at.comps;
         }
-        HOT_LAUNCH(this, "migrate_pack", k_pack_attr<int32_t>, div_up(n, 256), 256, 0, pGid.p, n, 1, lists.p, n, sendI.p, 1, 0);
+        HOT_LAUNCH(this, "migrate_pack", k_pack_attr<int32_t>, div_up(n, 256), 256, 0, pGid.p, n, 1, lists.p, n, sendI.p, NI, 0);
+        if (have_cls) HOT_LAUNCH(this, "migrate_pack", k_pack_attr<int32_t>, div_up(n, 256), 256, 0, pCls.p, n, 1, lists.p, n, sendI.p, NI, 1);
     }
     auto scaled = [&](const std::vector<int64_t>& v, int64_t f) {
         std::vector<int64_t> r(v);
@@ -786,7 +788,7 @@ void Ctx<T>::migrate_particles()
     {
         auto so = scaled(soff, NC * (int64_t)sizeof(T)), sb = scaled(scnt, NC * (int64_t)sizeof(T)), ro = scaled(roff, NC * (int64_t)sizeof(T)), rb = scaled(rcnt, NC * (int64_t)sizeof(T));
         c_alltoallv(sendT.p, so.data(), sb.data(), recvT.p, ro.data(), rb.data());
-        auto so4 = scaled(soff, 4), sb4 = scaled(scnt, 4), ro4 = scaled(roff, 4), rb4 = scaled(rcnt, 4);
+        auto so4 = scaled(soff, 4 * NI), sb4 = scaled(scnt, 4 * NI), ro4 = scaled(roff, 4 * NI), rb4 = scaled(rcnt, 4 * NI);
         c_alltoallv(sendI.p, so4.data(), sb4.data(), recvI.p, ro4.data(), rb4.data());
     }
     (void)nout;
@@ -802,11 +804,17 @@ void Ctx<T>::migrate_particles()
         }
         DBuf<int32_t> gid;
         gid.reserve(nnew, 1.25);
-        HOT_LAUNCH(this, "migrate_build", k_build_attr<int32_t>, div_up(nnew, 256), 256, 0, pGid.p, n, 1, keep, kept, recvI.p, 1, 0, gid.p, nnew);
+        HOT_LAUNCH(this, "migrate_build", k_build_attr<int32_t>, div_up(nnew, 256), 256, 0, pGid.p, n, 1, keep, kept, recvI.p, NI, 0, gid.p, nnew);
+        DBuf<int32_t> cls;
+        if (have_cls) {
+            cls.reserve(nnew, 1.25);
+            HOT_LAUNCH(this, "migrate_build", k_build_attr<int32_t>, div_up(nnew, 256), 256, 0, pCls.p, n, 1, keep, kept, recvI.p, NI, 1, cls.p, nnew);
+        }
         sync();
         k = 0;
         for (auto& at : attrs) std::swap(at.a->p, fresh[k].p), std::swap(at.a->cap, fresh[k].cap), ++k;
         std::swap(pGid.p, gid.p), std::swap(pGid.cap, gid.cap);
+        if (have_cls) std::swap(pCls.p, cls.p), std::swap(pCls.cap, cls.cap);
     }
     Np = nnew;
     reserve_particles(nnew); // the scratch / derived per-particle buffers (the nine attribute arrays above are large enough already)

@@ -292,6 +292,7 @@ void Ctx<T>::set_particles(int64_t n, const void* X, const void* V, const void* 
     HOT_CHECK(n > 0 && n < (1LL << index_bits), HOT_ERR_CAPACITY, "particle count must be in (0, 2^(32-block_bits)) (MpmSimulationBase.cpp:1071-1072)");
     need(X && V && m && vol && mu && lam, "X, V, mass, vol, mu, lambda are required");
     Np = n;
+    clear_plasticity_classes(); // a new particle set: classes are installed after it (hot_set_plasticity_classes)
     reserve_particles(n);
     auto put = [&](DBuf<T>& dst, const void* src, int comps) {
         if (comps == 1) {
@@ -330,6 +331,7 @@ void Ctx<T>::reserve_particles(int64_t n)
         pJp.reserve(n, slack);
     pFn.reserve(9 * n, slack), pFt.reserve(9 * n, slack), pStress.reserve(9 * n, slack), pGradV.reserve(9 * n, slack);
     spare1.reserve(n + 4, slack), spare3.reserve(3 * n + 4, slack), spare9.reserve(9 * n + 4, slack), sparei.reserve(n, slack), slot2orig.reserve(n, slack), pGid.reserve(n, slack);
+    if (have_cls) pCls.reserve(n, slack);
 }
 template <class T>
 void Ctx<T>::set_particle_ids(const int32_t* ids)
@@ -346,6 +348,92 @@ void Ctx<T>::get_particle_ids(int32_t* ids)
     HOT_LAUNCH(this, "soa_to_aos", k_soa_to_aos<int32_t>, div_up(Np, 256), 256, 0, pGid.p, sparei.p, slot2orig.p, Np, 1);
     HOT_HIP(hipMemcpyAsync(ids, sparei.p, (size_t)Np * sizeof(int32_t), hipMemcpyDefault, stream));
     sync();
+}
+
+// ---- per-particle plasticity classes
+// sorted[slot] = orig[slot2orig[slot]]
+__global__ void k_cls_from_orig(const int32_t* __restrict__ orig, const int32_t* __restrict__ slot2orig, int32_t* __restrict__ sorted, int64_t n)
+{
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) sorted[p] = orig[slot2orig[p]];
+}
+// out[0] = min, out[1] = max of a (out preset to INT_MAX, INT_MIN): one atomic pair per wavefront
+__global__ __launch_bounds__(256) void k_cls_range(const int32_t* __restrict__ a, int64_t n, int32_t* out)
+{
+    int lo = INT32_MAX, hi = INT32_MIN;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const int v = a[p];
+        lo = v < lo ? v : lo, hi = v > hi ? v : hi;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo, hi = h2 > hi ? h2 : hi;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMin(out, lo), atomicMax(out + 1, hi);
+}
+template <class T>
+int32_t Ctx<T>::max_particle_class(int32_t* min_out)
+{
+    int32_t* d = (int32_t*)(dscal.p + 220);
+    int32_t h[2] = { INT32_MAX, INT32_MIN };
+    HOT_HIP(hipMemcpyAsync(d, h, 8, hipMemcpyHostToDevice, stream));
+    HOT_LAUNCH(this, "cls_range", k_cls_range, std::min(div_up(Np, 256), 1024), 256, 0, pCls.p, Np, d);
+    HOT_HIP(hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, stream));
+    sync();
+    if (min_out) *min_out = h[0];
+    return h[1];
+}
+template <class T>
+void Ctx<T>::set_plasticity_classes(int32_t n, const hot_plasticity_class* classes, const int32_t* particle_class)
+{
+    need(Np > 0, "hot_set_plasticity_classes: call it after hot_set_particles");
+    need(n >= 0 && n <= PCLS_MAX, "hot_set_plasticity_classes: n must be between 0 and 16");
+    if (n == 0) { // back to hot_config.plasticity
+        clear_plasticity_classes();
+        return;
+    }
+    need(classes != nullptr, "hot_set_plasticity_classes: classes is NULL");
+    for (int k = 0; k < n; ++k) need(classes[k].kind >= 0 && classes[k].kind <= 2, "hot_set_plasticity_classes: a class's kind must be 0 (none), 1 (von Mises) or 2 (snow)");
+    need(particle_class || have_cls, "hot_set_plasticity_classes: particle_class is NULL and the context holds no classes");
+    // everything is checked before anything the context holds changes: a rejected call leaves it as it was
+    DBuf<int32_t> fresh;
+    if (particle_class) {
+        fresh.reserve(pGid.cap), sparei.reserve(Np);
+        HOT_HIP(hipMemcpyAsync(sparei.p, particle_class, (size_t)Np * sizeof(int32_t), hipMemcpyDefault, stream));
+        HOT_LAUNCH(this, "cls_from_orig", k_cls_from_orig, div_up(Np, 256), 256, 0, sparei.p, slot2orig.p, fresh.p, Np);
+        std::swap(pCls.p, fresh.p), std::swap(pCls.cap, fresh.cap);
+    }
+    int32_t lo = 0;
+    const int32_t hi = max_particle_class(&lo);
+    if (lo < 0 || hi >= n) {
+        if (particle_class) std::swap(pCls.p, fresh.p), std::swap(pCls.cap, fresh.cap);
+        need(false, particle_class ? "hot_set_plasticity_classes: a particle class lies outside [0, n)" : "hot_set_plasticity_classes: particle_class is NULL and the context holds a class >= n");
+    }
+    T tab[PCLS_MAX * PCLS_STRIDE] = {};
+    for (int k = 0; k < n; ++k) {
+        T* t = tab + PCLS_STRIDE * k;
+        t[0] = (T)classes[k].kind, t[1] = (T)classes[k].yield_stress;
+        for (int j = 0; j < 5; ++j) t[2 + j] = (T)classes[k].snow[j];
+        cls_host[k] = classes[k];
+    }
+    clsTab.reserve(PCLS_MAX * PCLS_STRIDE);
+    HOT_HIP(hipMemcpyAsync(clsTab.p, tab, sizeof(tab), hipMemcpyHostToDevice, stream));
+    sync(); // (tab is a local)
+    have_cls = true, ncls = n;
+}
+template <class T>
+void Ctx<T>::get_plasticity_classes(int32_t* n, hot_plasticity_class* classes, int32_t* particle_class)
+{
+    if (n) *n = ncls;
+    if (classes)
+        for (int k = 0; k < ncls; ++k) classes[k] = cls_host[k];
+    if (particle_class) {
+        need(have_cls, "hot_get_plasticity_classes: the context holds no particle classes");
+        HOT_LAUNCH(this, "soa_to_aos", k_soa_to_aos<int32_t>, div_up(Np, 256), 256, 0, pCls.p, sparei.p, slot2orig.p, Np, 1);
+        HOT_HIP(hipMemcpyAsync(particle_class, sparei.p, (size_t)Np * sizeof(int32_t), hipMemcpyDefault, stream));
+        sync();
+    }
 }
 
 template <class T>
@@ -412,6 +500,11 @@ void Ctx<T>::sort()
     HOT_LAUNCH(this, "reorder_gather", k_gather<int32_t>, div_up(n, 256), 256, 0, pGid.p, sparei.p, vals2.p, n, 1);
     std::swap(pGid.p, sparei.p);
     std::swap(pGid.cap, sparei.cap);
+    if (have_cls) { // the plasticity classes stay with their particles
+        HOT_LAUNCH(this, "reorder_gather", k_gather<int32_t>, div_up(n, 256), 256, 0, pCls.p, sparei.p, vals2.p, n, 1);
+        std::swap(pCls.p, sparei.p);
+        std::swap(pCls.cap, sparei.cap);
+    }
     // groups
     HOT_LAUNCH(this, "group_heads", k_group_heads, div_up(n, 256), 256, 0, keys2.p, flags.p, n);
     Ng = exclusive_scan_i32(flags.p, scan.p, n);

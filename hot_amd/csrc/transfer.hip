@@ -13,7 +13,8 @@
 //                  (ImplicitSolver.h:474-477).
 //   k_g2p          constructNewVelocityFromNewtonResult (:891-901) + gridToParticlesHelper<true,false,false>
 //                  (:930-1007) + evolveStrain (Force/FBasedMpmForceHelper.cpp:99-114) + applyPlasticity (:1044-1064)
-//                  fused: node tile staged in LDS, particle streams fully coalesced.
+//                  fused: node tile staged in LDS, particle streams fully coalesced.  Two overloads of one body (transfer_g2p_body.h):
+//                  hot_config.plasticity for every particle, or the return mapping of each particle's class (hot_set_plasticity_classes).
 #include "hot_impl.h"
 #include "hot_constitutive.h"
 
@@ -650,152 +651,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     const int32_t* __restrict__ group_nb, const int32_t* __restrict__ gIdx, const T* __restrict__ nodeV, const T* __restrict__ dv, T dx, T one_over_dx, T dt, T apic_r,
     T cfl, T yield_stress, T sn0, T sn1, T sn2, T sn3, T sn4, int32_t* flags_out)
 {
-    using G = Geo<T>;
-    constexpr int TY = G::BY + 2, TZ = G::BZ + 2, TILE = (G::BX + 2) * TY * TZ;
-    __shared__ T nv[3][TILE];
-    const int g = blockIdx.x;
-    const int first = group_first[g], last = group_first[g + 1];
-    // the position of this thread's first particle is requested before the tile gather, and the tile's DOF ids come from the per-group
-    // table (tileDof) instead of the nb8 -> gIdx chain: the workgroup's dependent round trips (indices -> nodal values, particle data)
-    // run side by side.  Fn is NOT held across the 27-node loop (round 3: with it the fp64 kernel needed 214 registers, two wavefronts
-    // per SIMD; it is read after the loop, when only the 21 sums are live, and the other wavefronts cover that round trip).
-    const int p0 = first + threadIdx.x;
-    T xpre[3] = { 0, 0, 0 };
-    if (p0 < last) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) xpre[d] = X[(int64_t)d * Np + p0];
-    }
-    for (int t = threadIdx.x; t < TILE; t += 256) {
-        int idx = gIdx[(int64_t)g * TILE + t]; // gIdx here = tileDof
-        T a = 0, b = 0, c = 0;
-        if (idx >= 0) {
-            a = nodeV[3 * idx] + dv[3 * idx], b = nodeV[3 * idx + 1] + dv[3 * idx + 1], c = nodeV[3 * idx + 2] + dv[3 * idx + 2];
-        }
-        nv[0][t] = a, nv[1][t] = b, nv[2][t] = c;
-    }
-    __syncthreads();
-    const int ox = group_origin[3 * g], oy = group_origin[3 * g + 1], oz = group_origin[3 * g + 2];
-    const T D_inverse = (T)4 / (dx * dx);
-    int myflags = 0;
-    for (int p = first + threadIdx.x; p < last; p += 256) {
-        T xp[3];
-        if (p == p0) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) xp[d] = xpre[d];
-        }
-        else { // groups of more than 256 particles
-#pragma unroll
-            for (int d = 0; d < 3; ++d) xp[d] = X[(int64_t)d * Np + p];
-        }
-        int base[3];
-        T w[3][3], dw[3][3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) bspline<T>(one_over_dx, xp[d], base[d], w[d], dw[d]);
-        const int cx = base[0] - ox, cy = base[1] - oy, cz = base[2] - oz;
-        T pic[3] = { 0, 0, 0 };
-        T B[9], gv[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) B[c] = (T)0, gv[c] = (T)0;
-        if constexpr (FACT) {
-            T wz[3], wd2[3], dwz[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) wz[k] = w[2][k], wd2[k] = w[2][k] * ((T)(base[2] + k) * dx - xp[2]), dwz[k] = one_over_dx * dw[2][k];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const T wi = w[0][i], dwi = one_over_dx * dw[0][i];
-                const T d0 = (T)(base[0] + i) * dx - xp[0];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int t = ((cx + i) * TY + (cy + j)) * TZ + cz;
-                    T s0[3], s1[3], s2[3]; // column sums: sum_k w_k v, sum_k w_k d2_k v, sum_k dw_k / dx v
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const T va = nv[c][t], vb = nv[c][t + 1], vc = nv[c][t + 2];
-                        s0[c] = fma(wz[2], vc, fma(wz[1], vb, wz[0] * va));
-                        s1[c] = fma(wd2[2], vc, fma(wd2[1], vb, wd2[0] * va));
-                        s2[c] = fma(dwz[2], vc, fma(dwz[1], vb, dwz[0] * va));
-                    }
-                    const T wij = wi * w[1][j], gi = dwi * w[1][j], gj = wi * (one_over_dx * dw[1][j]);
-                    const T d1 = (T)(base[1] + j) * dx - xp[1];
-                    const T a0 = wij * d0, a1 = wij * d1;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        pic[c] = fma(wij, s0[c], pic[c]);
-                        B[c] = fma(a0, s0[c], B[c]), B[3 + c] = fma(a1, s0[c], B[3 + c]), B[6 + c] = fma(wij, s1[c], B[6 + c]);
-                        gv[c] = fma(gi, s0[c], gv[c]), gv[3 + c] = fma(gj, s0[c], gv[3 + c]), gv[6 + c] = fma(wij, s2[c], gv[6 + c]);
-                    }
-                }
-            }
-        }
-        else {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            T wi = w[0][i], dwi = one_over_dx * dw[0][i];
-            T d0 = (T)(base[0] + i) * dx - xp[0];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                T wij = wi * w[1][j];
-                T dwij_i = dwi * w[1][j], dwij_j = wi * one_over_dx * dw[1][j];
-                T d1 = (T)(base[1] + j) * dx - xp[1];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    T wijk = wij * w[2][k];
-                    T g0 = dwij_i * w[2][k], g1 = dwij_j * w[2][k], g2 = wij * one_over_dx * dw[2][k];
-                    T d2 = (T)(base[2] + k) * dx - xp[2];
-                    int t = ((cx + i) * TY + (cy + j)) * TZ + (cz + k);
-                    T v0 = nv[0][t], v1 = nv[1][t], v2 = nv[2][t];
-                    pic[0] += wijk * v0, pic[1] += wijk * v1, pic[2] += wijk * v2;
-                    T wv0 = wijk * v0, wv1 = wijk * v1, wv2 = wijk * v2;
-                    B[0] += wv0 * d0, B[1] += wv1 * d0, B[2] += wv2 * d0;
-                    B[3] += wv0 * d1, B[4] += wv1 * d1, B[5] += wv2 * d1;
-                    B[6] += wv0 * d2, B[7] += wv1 * d2, B[8] += wv2 * d2;
-                    gv[0] += v0 * g0, gv[1] += v1 * g0, gv[2] += v2 * g0;
-                    gv[3] += v0 * g1, gv[4] += v1 * g1, gv[5] += v2 * g1;
-                    gv[6] += v0 * g2, gv[7] += v1 * g2, gv[8] += v2 * g2;
-                }
-            }
-        }
-        }
-        Mat3<T> Fo;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) Fo.a[c] = Fn[(int64_t)c * Np + p];
-        V[p] = pic[0], V[Np + p] = pic[1], V[2 * Np + p] = pic[2];
-        T ra = (apic_r + (T)1) * (T)0.5, rb = (apic_r - (T)1) * (T)0.5;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) C[(int64_t)(c * 3 + r) * Np + p] = ra * (B[c * 3 + r] * D_inverse) + rb * (B[r * 3 + c] * D_inverse);
-        T inc0 = dt * pic[0], inc1 = dt * pic[1], inc2 = dt * pic[2];
-        X[p] = xp[0] + inc0, X[Np + p] = xp[1] + inc1, X[2 * Np + p] = xp[2] + inc2;
-        T inc = inc0 * inc0 + inc1 * inc1 + inc2 * inc2, dx2 = dx * dx;
-        if (inc > dx2) myflags |= 1;
-        if (inc > dx2 * (T)0.25 * (cfl * cfl)) myflags |= 2;
-        if (gradV_out)
-#pragma unroll
-            for (int c = 0; c < 9; ++c) gradV_out[(int64_t)c * Np + p] = gv[c];
-        // F = (I + dt gradV) Fn   (restoreStrain + evolveStrain)
-        Mat3<T> A, Fnew;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) A.a[c] = dt * gv[c] + ((c % 4 == 0) ? (T)1 : (T)0);
-        Fnew = m3_mul(A, Fo);
-        if (PLASTIC == 1) {
-            von_mises_project(Fnew, Mu[p], Lam[p], yield_stress);
-        }
-        else if (PLASTIC == 2) {
-            T mu = Mu[p], la = Lam[p], jp = Jp[p];
-            snow_project(Fnew, mu, la, jp, sn0, sn1, sn2, sn3, sn4);
-            Mu[p] = mu, Lam[p] = la, Jp[p] = jp;
-        }
-#pragma unroll
-        for (int c = 0; c < 9; ++c) F[(int64_t)c * Np + p] = Fnew.a[c];
-    }
-    // one global atomic per wavefront at most (2 M same-address atomics cost more than the whole transfer)
-    unsigned long long m1 = __ballot(myflags & 1), m2 = __ballot(myflags & 2);
-    if ((threadIdx.x & 63) == 0 && (m1 | m2)) {
-        int bits = (m1 ? 1 : 0) | (m2 ? 2 : 0);
-        int cur = __hip_atomic_load(flags_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((cur & bits) != bits) atomicOr(flags_out, bits); // already-set bits need no further traffic
-    }
+    static_assert(PLASTIC >= 0 && PLASTIC <= 2, "per-particle classes: the overload below");
+    constexpr const int32_t* pcls = nullptr;
+    constexpr const T* cls_tab = nullptr;
+#include "transfer_g2p_body.h"
+}
+// k_g2p<T, 3, FACT>: per-particle plasticity classes, launched only while a class table is installed (profile label g2p_classes).  Both return mappings
+// hang off one SVD (plasticity_classes_project, hot_constitutive.h).  fp64 asks for two wavefronts per SIMD where its siblings ask for three: the
+// SVD with Fnew, U, V, the singular values and a class's parameters live does not fit three wavefronts' 168 registers (this kernel spills 14 there,
+// k_g2p<double, 2> 22), and a new kernel may not use scratch (tests/test_kernel_resources.py).  What that costs: profiles/plasticity_classes.txt, DESIGN.md §12.
+template <class T, int PLASTIC, bool FACT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 8 ? 2 : 3))) void k_g2p(T* __restrict__ X, T* __restrict__ V, T* __restrict__ C, T* __restrict__ F, const T* __restrict__ Fn,
+    T* __restrict__ gradV_out, T* __restrict__ Mu, T* __restrict__ Lam, T* __restrict__ Jp, int64_t Np, const int32_t* __restrict__ group_first, const int32_t* __restrict__ group_origin,
+    const int32_t* __restrict__ group_nb, const int32_t* __restrict__ gIdx, const T* __restrict__ nodeV, const T* __restrict__ dv, T dx, T one_over_dx, T dt, T apic_r, T cfl, int32_t* flags_out,
+    const int32_t* __restrict__ pcls, const T* __restrict__ cls_tab)
+{
+    static_assert(PLASTIC == 3, "one mapping for every particle: the overload above");
+    constexpr T yield_stress = 0, sn0 = 0, sn1 = 0, sn2 = 0, sn3 = 0, sn4 = 0;
+#include "transfer_g2p_body.h"
 }
 
 template <class T>
@@ -809,6 +682,18 @@ void Ctx<T>::g2p(double dt_, int32_t* flags)
     if (halo_mode()) halo_gather(*levels[0], dv.p); // dv at the nodes of this rank's particle tiles that other ranks own
 #define G2P_ARGS pX.p, pV.p, pC.p, pF.p, pFn.p, (keep_debug ? pGradV.p : (T*)nullptr), pMu.p, pLam.p, pJp.p, Np, group_first.p, group_origin.p, group_nb.p, tileDof.p, nodeV.p, dv.p, dx, \
                  one_over_dx, (T)dt_, (T)cfg.apic_rpic_ratio, (T)cfg.cfl, (T)cfg.yield_stress, (T)cfg.snow[0], (T)cfg.snow[1], (T)cfg.snow[2], (T)cfg.snow[3], (T)cfg.snow[4], dflags
+    if (ncls > 0) { // a class table is installed: cfg.plasticity / yield_stress / snow are not consulted
+#define G2P_CLS_ARGS pX.p, pV.p, pC.p, pF.p, pFn.p, (keep_debug ? pGradV.p : (T*)nullptr), pMu.p, pLam.p, pJp.p, Np, group_first.p, group_origin.p, group_nb.p, tileDof.p, nodeV.p, dv.p, dx, \
+                     one_over_dx, (T)dt_, (T)cfg.apic_rpic_ratio, (T)cfg.cfl, dflags, pCls.p, clsTab.p
+#ifdef HOT_AB_KERNELS
+        if (ab_flag("HOT_G2P_V1"))
+            HOT_LAUNCH(this, "g2p_classes", (k_g2p<T, 3, false>), Ng, 256, 0, G2P_CLS_ARGS);
+        else
+#endif
+        HOT_LAUNCH(this, "g2p_classes", (k_g2p<T, 3, true>), Ng, 256, 0, G2P_CLS_ARGS);
+#undef G2P_CLS_ARGS
+    }
+    else
 #ifdef HOT_AB_KERNELS
     if (ab_flag("HOT_G2P_V1")) { // node-by-node sums
         if (cfg.plasticity == 1)

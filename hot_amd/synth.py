@@ -70,6 +70,50 @@ def cube_slab(n, x0, x1, ppc=8, dx=0.01, corner=(5.0, 5.0, 5.0), E=5e4, nu=0.3, 
                 index=(np.concatenate(ids) if ids else np.zeros(0, np.int64)))
 
 
+# the reference's snow-wedge scene (Projects/multigrid/MultigridInit3D.h:1216-1244): SnowPlasticity(hardening 10, theta_c 2.5e-2, theta_s 7.5e-3, Jp in [0.1, 50])
+# on a block of rho 400, E 1.4e5, nu 0.2; the sphere dropped on it is CorotatedIsotropic(1e8, nu) without plasticity
+SNOW_WEDGE = dict(rho=400.0, E=1.4e5, nu=0.2, E_ball=1e8, snow=(10.0, 2.5e-2, 7.5e-3, 0.1, 50.0))
+
+
+def two_body_cloud(n=8, ppc=8, dx=0.01, corner=(5.0, 5.0, 5.0), dtype=np.float64, seed=123, noise=0.02, ball_velocity=(0.0, -1.0, 0.0), **material):
+    """A snow block with a stiff elastic ball above it, in the proportions of the reference's snow-wedge scene (a 0.4 x 0.2 x 0.2 block, a sphere of
+    radius 0.05 whose centre hangs 0.1 above the block's top): a (2n, n, n)-cell block at `corner`, a ball of radius n / 4 cells centred n / 2 cells
+    above the middle of its top face.  Per-particle mu / lam (the two bodies differ by E), "cls": 0 for the block, 1 for the ball, and
+    "classes": the matching table for Context.set_plasticity_classes (class 0 snow, class 1 none).  The block's velocities carry Gaussian noise,
+    the ball moves with ball_velocity; caller order is shuffled."""
+    m = dict(SNOW_WEDGE, **material)
+    fx, fy, fz = _FACT[ppc]
+    rng = np.random.default_rng(seed)
+    cells = (2 * n, n, n)
+    r_cells = n / 4.0
+    centre = np.array([n, n + n / 2.0, n / 2.0])  # in cells, relative to the corner
+
+    def sample(cell):
+        si, sj, sk = np.meshgrid(np.arange(fx), np.arange(fy), np.arange(fz), indexing="ij")
+        sub = np.stack([si.ravel() / fx, sj.ravel() / fy, sk.ravel() / fz], 1)
+        ext = np.array([1.0 / fx, 1.0 / fy, 1.0 / fz])
+        jit = 0.1 + 0.8 * rng.random((cell.shape[0], ppc, 3))
+        return (cell[:, None, :] + sub[None, :, :] + jit * ext[None, None, :]).reshape(-1, 3)
+
+    ci, cj, ck = np.meshgrid(np.arange(cells[0]), np.arange(cells[1]), np.arange(cells[2]), indexing="ij")
+    Xb = sample(np.stack([ci.ravel(), cj.ravel(), ck.ravel()], 1).astype(np.float64))
+    lo, hi = np.floor(centre - r_cells).astype(int), np.ceil(centre + r_cells).astype(int)
+    ci, cj, ck = np.meshgrid(*(np.arange(lo[d], hi[d]) for d in range(3)), indexing="ij")
+    Xs = sample(np.stack([ci.ravel(), cj.ravel(), ck.ravel()], 1).astype(np.float64))
+    Xs = Xs[((Xs - centre[None, :]) ** 2).sum(1) <= r_cells ** 2]
+    X = np.concatenate([Xb, Xs]) * dx + np.asarray(corner)
+    cls = np.concatenate([np.zeros(len(Xb), np.int32), np.ones(len(Xs), np.int32)])
+    V = np.concatenate([noise * rng.standard_normal((len(Xb), 3)), np.tile(np.asarray(ball_velocity, np.float64), (len(Xs), 1))])
+    perm = rng.permutation(len(X))
+    X, V, cls = X[perm], V[perm], cls[perm]
+    Np = len(X)
+    (mu0, lam0), (mu1, lam1) = lame(m["E"], m["nu"]), lame(m["E_ball"], m["nu"])
+    T = dtype
+    return dict(X=X.astype(T), V=V.astype(T), mass=np.full(Np, m["rho"] * dx ** 3 / ppc, T), vol=np.full(Np, dx ** 3 / ppc, T),
+                mu=np.where(cls == 0, mu0, mu1).astype(T), lam=np.where(cls == 0, lam0, lam1).astype(T), dx=dx, cls=cls,
+                classes=[dict(kind=2, snow=tuple(m["snow"])), dict(kind=0)])
+
+
 def sticky_floor(corner_y, dx, layers=2):
     """Half space {y <= corner_y + (layers-0.5)*dx}: the bottom `layers` node layers of a cloud whose lowest
     cell starts at corner_y (node layer k sits at corner_y + k*dx ... the kernel reaches one layer below)."""

@@ -82,6 +82,12 @@ public:
     {
         check(ctx, hot_set_particles(ctx, Np, X, V, mass, C, F, vol, mu, lambda, Jp), "hot_set_particles");
     }
+    // MpmParticleHandleBase::addPlasticity, per body: a table of up to 16 plasticity classes (kind 0 none / 1 VonMisesFixedCorotated / 2 SnowPlasticity) and one
+    // class per particle in the order of the call above; particle_class = nullptr keeps the classes the context holds (after readRestart); n = 0 removes the table
+    void setPlasticityClasses(int n, const hot_plasticity_class* classes, const int32_t* particle_class)
+    {
+        check(ctx, hot_set_plasticity_classes(ctx, n, classes, particle_class), "hot_set_plasticity_classes");
+    }
     void getParticles(T* X, T* V, T* C, T* F, T* mu = nullptr, T* lambda = nullptr, T* Jp = nullptr) { check(ctx, hot_get_particles(ctx, X, V, C, F, mu, lambda, Jp), "hot_get_particles"); }
     void sortParticlesAndPolluteGrid() { check(ctx, hot_sort(ctx), "hot_sort"); }
     void particlesToGrid() { check(ctx, hot_p2g(ctx), "hot_p2g"); }

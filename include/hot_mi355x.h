@@ -353,6 +353,27 @@ int hot_constitutive_eval(hot_ctx*, int32_t n, const void* F /*9n*/, const void*
 int hot_plasticity_eval(hot_ctx*, int32_t kind /*1 von Mises, 2 snow*/, int32_t n, void* F /*9n in/out*/, void* mu /*n in/out*/, void* lambda /*n in/out*/,
     void* Jp /*n in/out, snow only*/);
 
+/* ---- per-particle plasticity classes, HIP product only: the reference attaches a plasticity applier to ONE particle handle and applyPlasticity touches
+ *      only the particles that carry it (Lib/Ziran/Physics/PlasticityApplier.h:36-53, Lib/MPM/MpmSimulationBase.cpp:1044-1064), so one scene mixes
+ *      elastic, von Mises and snow bodies.  A table of n <= 16 classes and one class index per particle (order of hot_set_particles / hot_get_particles;
+ *      a sharded context: of its current particles, ascending global id).  With a table installed hot_g2p applies to every particle the return mapping of
+ *      its class and ignores cfg.plasticity / cfg.yield_stress / cfg.snow (hot_plasticity_eval keeps using cfg); n = 0 removes the table.  Call after
+ *      hot_set_particles, which clears the table, as does hot_read_restart of a file without a class column.  The classes travel with their particles
+ *      (hot_sort, migration between ranks, restart files: array "plasticity class"); the parameter table is not particle data: after hot_read_restart
+ *      install it again with particle_class = NULL.  HOT_ERR_INVALID: a kind outside 0 / 1 / 2, n > 16, a particle class outside [0, n), a NULL
+ *      particle_class when the context holds no classes or one >= n.  hot_get_plasticity_classes: any output may be NULL.
+ *      hot_plasticity_eval_classes applies the installed table to caller-supplied samples in place (layouts of hot_plasticity_eval, cls: the sample's
+ *      class) through the device functions hot_g2p uses. */
+typedef struct hot_plasticity_class {
+    int32_t kind; /* 0 none (elastic), 1 VonMisesFixedCorotated, 2 SnowPlasticity */
+    int32_t reserved;
+    double yield_stress; /* kind 1 */
+    double snow[5]; /* kind 2: psi, theta_c, theta_s, min_Jp, max_Jp */
+} hot_plasticity_class; /* 56 bytes */
+int hot_set_plasticity_classes(hot_ctx*, int32_t n, const hot_plasticity_class* classes /*n*/, const int32_t* particle_class /*Np, or NULL: keep the classes the context holds*/);
+int hot_get_plasticity_classes(hot_ctx*, int32_t* n, hot_plasticity_class* classes /*>= 16, or NULL*/, int32_t* particle_class /*Np, or NULL*/);
+int hot_plasticity_eval_classes(hot_ctx*, int32_t n, void* F /*9n in/out*/, void* mu /*n in/out*/, void* lambda /*n in/out*/, void* Jp /*n in/out*/, const int32_t* cls /*n*/);
+
 /* ---- frame output (SimulationBase::write -> MpmSimulationBase::writeState, Lib/Ziran/Sim/SimulationBase.h:152-190,
  *      Lib/MPM/MpmSimulationBase.cpp:754-785): hot_write_partio = writePartio's .bgeo of the particle positions (PartioIO.h:142-180);
  *      hot_write_restart / hot_read_restart = the particle DataManager in the container layout of DataManager::writeData

@@ -73,7 +73,8 @@ ABI_VERSION = 7  # include/hot_mi355x.h HOT_ABI_VERSION: the layout of hot_confi
 
 # declared by the header for the HIP product only (device-runtime services a host-memory implementation of the ABI has no use for)
 PRODUCT_ONLY_SYMBOLS = ["rccl_unique_id", "rccl_attach", "rccl_selftest", "get_level_inblock_nnzb", "copy_bandwidth",
-                        "set_plasticity_classes", "get_plasticity_classes", "plasticity_eval_classes"]
+                        "set_plasticity_classes", "get_plasticity_classes", "plasticity_eval_classes",
+                        "set_preconditioner_dtype", "get_preconditioner_dtype"]
 
 
 class HotError(RuntimeError):
@@ -191,7 +192,11 @@ class HotLib:
         return self.fn["version"]().decode()
 
     def context(self, cfg=None, **kw):
-        return Context(self, cfg if cfg is not None else self.default_config(**kw))
+        pdt = kw.pop("preconditioner_dtype", None)  # not a hot_config field: hot_set_preconditioner_dtype on the new context
+        ctx = Context(self, cfg if cfg is not None else self.default_config(**kw))
+        if pdt is not None:
+            ctx.set_preconditioner_dtype(pdt)
+        return ctx
 
 
 class Context:
@@ -625,6 +630,17 @@ class Context:
         cls = np.ascontiguousarray(np.broadcast_to(cls, (n,)), np.int32)
         self._product_call("plasticity_eval_classes", [C.c_void_p, C.c_int32] + [C.c_void_p] * 5, C.c_int32(n), _ptr(F), _ptr(mu), _ptr(lam), _ptr(Jp), _ptr(cls))
         return F, mu, lam, Jp
+
+    # ---- precision of the multigrid hierarchy the preconditioner runs on (HIP product only)
+    def set_preconditioner_dtype(self, dtype):
+        """1: the context's own precision (default); 0: an fp32 hierarchy inside an fp64 context.  Takes effect at the next build_mg."""
+        self._product_call("set_preconditioner_dtype", [C.c_void_p, C.c_int32], C.c_int32(int(dtype)))
+
+    @property
+    def preconditioner_dtype(self):
+        d = C.c_int32()
+        self._product_call("get_preconditioner_dtype", [C.c_void_p, C.POINTER(C.c_int32)], C.byref(d))
+        return d.value
 
     def advance(self, dt):
         st = hot_stats()

@@ -105,7 +105,7 @@ int hot_sync(hot_ctx* ctx)
 {
     HOT_API_BEGIN
     HOT_HIP(hipStreamSynchronize(ctx->impl->stream));
-    ctx->impl->prof.collect();
+    ctx->impl->prof_collect();
     HOT_API_END
 }
 int hot_set_particles(hot_ctx* ctx, int64_t Np, const void* X, const void* V, const void* mass, const void* C, const void* F, const void* vol, const void* mu, const void* lambda, const void* Jp)
@@ -442,6 +442,19 @@ int hot_plasticity_eval_classes(hot_ctx* ctx, int32_t n, void* F, void* mu, void
     ctx->impl->plasticity_eval_classes(n, F, mu, lambda, Jp, cls);
     HOT_API_END
 }
+int hot_set_preconditioner_dtype(hot_ctx* ctx, int32_t dtype)
+{
+    HOT_API_BEGIN
+    ctx->impl->set_preconditioner_dtype(dtype);
+    HOT_API_END
+}
+int hot_get_preconditioner_dtype(hot_ctx* ctx, int32_t* dtype)
+{
+    HOT_API_BEGIN
+    HOT_CHECK(dtype, HOT_ERR_INVALID, "hot_get_preconditioner_dtype: dtype is NULL");
+    *dtype = ctx->impl->get_preconditioner_dtype();
+    HOT_API_END
+}
 int hot_advance(hot_ctx* ctx, double dt, hot_stats* stats)
 {
     HOT_API_BEGIN
@@ -464,7 +477,7 @@ int hot_profile_reset(hot_ctx* ctx)
 {
     HOT_API_BEGIN
     HOT_HIP(hipStreamSynchronize(ctx->impl->stream));
-    ctx->impl->prof.collect();
+    ctx->impl->prof_collect();
     ctx->impl->prof.recs.clear();
     HOT_API_END
 }
@@ -472,7 +485,7 @@ int hot_profile_count(hot_ctx* ctx, int32_t* n)
 {
     HOT_API_BEGIN
     HOT_HIP(hipStreamSynchronize(ctx->impl->stream));
-    ctx->impl->prof.collect();
+    ctx->impl->prof_collect();
     *n = (int32_t)ctx->impl->prof.recs.size();
     HOT_API_END
 }

@@ -54,6 +54,11 @@ struct DBuf {
         cap = (size_t)(n * slack) + 64;
         HOT_HIP(hipMalloc((void**)&p, cap * sizeof(T)));
     }
+    void release() // give the memory back (hipFree waits for the device)
+    {
+        if (p) HOT_HIP(hipFree(p));
+        p = nullptr, cap = 0;
+    }
     operator T*() const { return p; }
 };
 

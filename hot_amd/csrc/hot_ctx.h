@@ -70,6 +70,18 @@ struct CtxBase {
     hipStream_t stream = nullptr;
     Profiler prof;
     hot_stats stats;
+    CtxBase* prof_child = nullptr; // a context inside this one whose launches are reported under this one's profile (the fp32 hierarchy of mixed precision)
+    void prof_collect() // the finished launches of this context and of prof_child, summed by label into this context's records
+    {
+        prof.collect();
+        if (!prof_child) return;
+        prof_child->prof.collect();
+        for (auto& kv : prof_child->prof.recs) {
+            auto& r = prof.recs[kv.first];
+            r.calls += kv.second.calls, r.ms += kv.second.ms;
+        }
+        prof_child->prof.recs.clear();
+    }
     virtual ~CtxBase()
     {
         if (native_comm && native_comm_free) native_comm_free(native_comm);
@@ -122,6 +134,8 @@ struct CtxBase {
     virtual void set_plasticity_classes(int32_t n, const hot_plasticity_class* classes, const int32_t* particle_class) = 0;
     virtual void get_plasticity_classes(int32_t* n, hot_plasticity_class* classes, int32_t* particle_class) = 0;
     virtual void plasticity_eval_classes(int32_t n, void* F, void* mu, void* lambda, void* Jp, const int32_t* cls) = 0;
+    virtual void set_preconditioner_dtype(int32_t dtype) = 0;
+    virtual int32_t get_preconditioner_dtype() = 0;
     virtual void advance(double dt, hot_stats* st) = 0;
     virtual void calculate_dt(double max_dt, double* dt, double* max_speed, double* min_corner, double* max_corner) = 0;
     virtual void advance_frame(double frame_dt, double min_dt, double max_dt, int32_t* substeps, int32_t* iterations_total, hot_stats* st) = 0;

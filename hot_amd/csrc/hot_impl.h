@@ -140,6 +140,15 @@ struct Level {
     bool l1 = false;
     const T* gs_d() const { return l1 ? gsD.p : diagVal.p; }
     const T* gs_dinv() const { return l1 ? gsDinv.p : diagBlockInv.p; }
+    // give back what only hot_build_mg prepares on a level (colouring, GS structures, A P, transfer tables, work vectors): a level 0 whose
+    // preconditioner runs on another context's hierarchy (mixed precision) keeps its matrix and diagonals only
+    void release_hierarchy()
+    {
+        ckey.release(), gs_order.release(), gs_block_start.release(), apv.release(), apc.release(), gs_pad.release(), gs_col.release(), gs_img.release(), gs_imgi.release();
+        gs_p1.release(), gs_slot.release(), gs_rowpn.release(), gs_srec.release(), gs_w.release(), rowcnt.release(), pcol.release(), pw.release();
+        hkeys.release(), hrank.release(), hid.release(), residual.release(), initialResidual.release(), sol.release(), du.release(), dAu.release(), tmp.release();
+        gs_img_ready = gs_fused_ready = gs_w_ready = built = split = colored = false;
+    }
     // ---- halo mode (hot_config.shard_replicated == 0): the entries of a DOF vector of this level this rank reads but does not own, and
     // who owns them; both lists are ordered by (owner | reader, colour, position in gs_order), so one colour of a GS sweep is a sub-range
     struct Halo {
@@ -366,14 +375,15 @@ struct Ctx : CtxBase {
             __builtin_ia32_pause();
             if ((spin & 1023u) == 1023u && wall_ms() - t0 > 20.0) {
                 HOT_HIP(hipStreamSynchronize(stream));
-                if (*(volatile int*)(hscal + 250) != 0) sync(); // a spinning kernel (k_gs_sweep, k_cg_persist) gave up: throws ERR_RETRY, the caller redoes the operation with launches
+                if (*(volatile int*)(hscal + 250) != 0 || shadow_timed_out()) sync(); // a spinning kernel (k_gs_sweep, k_cg_persist) gave up: throws ERR_RETRY, the caller redoes the operation with launches
                 HOT_CHECK(*t == want, HOT_ERR_DEVICE, "a reduction launch did not deliver its result");
                 break;
             }
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        if (*(volatile int*)(hscal + 250) != 0) sync(); // k_gs_sweep timed out somewhere before: the usual path (throws ERR_RETRY)
+        if (*(volatile int*)(hscal + 250) != 0 || shadow_timed_out()) sync(); // k_gs_sweep timed out somewhere before: the usual path (throws ERR_RETRY)
     }
+    bool shadow_timed_out() const { return mg32 && *(volatile int*)(mg32->hscal + 250) != 0; } // a spinning kernel of the fp32 hierarchy gave up
     DBuf<uint64_t> col_hk; // mark_colors scratch (block hash map, colour block heads)
     DBuf<unsigned long long> col_hr;
     DBuf<int32_t> col_hi, col_cb;
@@ -406,6 +416,7 @@ struct Ctx : CtxBase {
     }
     void release_levels(size_t keep = 0)
     {
+        if (keep == 0 && mg32) drop_mixed(); // the fp32 hierarchy of mixed precision goes with the level 0 it was built from (into the shadow's pool)
         while (levels.size() > keep) {
             Level<T>* l = levels.back();
             levels.pop_back();
@@ -418,7 +429,53 @@ struct Ctx : CtxBase {
     DBuf<int32_t> orig2slot; // inverse of slot2orig
     Ctx<T>* build_gmg_grid(int level); // sort / mass P2G / boundaries / re-rasterised matrix of coarse level `level`
 
-    Ctx(const hot_config& c);
+    // ---- mixed precision (hot_set_preconditioner_dtype): an fp64 context whose preconditioner runs on an fp32 hierarchy.  The hierarchy
+    // belongs to a shadow Ctx<float> inside this context (like gmg's grids): same stream, same deterministic flag, its own pinned host block (tickets,
+    // time-out flag), level pool and GS state.  The shadow's level 0 is this context's level 0 rounded to nearest; levels >= 1 exist only there.
+    int precond_dtype = 1; // as set: 1 = the context's own precision, 0 = fp32
+    Ctx<float>* mg32 = nullptr; // the shadow (created by the first mixed hot_build_mg, kept for its pools)
+    bool mg32_on = false; // the hierarchy built last is the shadow's
+    bool is_shadow = false; // this context is one: the stream is the parent's
+    const volatile double* in_scale_h = nullptr; // shadow: pinned host word holding the power of two the V-cycle's input was divided by (absolute stopping tests undo it)
+    DBuf<T> mg32_io[3]; // shadow: fp32 images of the vectors that cross the boundary
+    std::function<void(T*, T*, T*)> vcycle_head; // shadow: launches the head of a V-cycle (residual, second copy or null, cleared output) in place of k_vcycle_start
+    bool mixed() const { return mg32_on && mg32 != nullptr; }
+    int nlevels() const { return mixed() ? (int)mg32->levels.size() : (int)levels.size(); }
+    void set_preconditioner_dtype(int32_t dtype) override;
+    int32_t get_preconditioner_dtype() override { return sizeof(T) == 4 ? 0 : precond_dtype; }
+    void check_mixed_allowed(); // HOT_ERR_INVALID for what mixed precision does not combine with
+    void build_mg_mixed(); // mg_build.hip
+    void drop_mixed() // the shadow's levels go back to its pool
+    {
+        if (mg32) mg32->release_levels(0);
+        mg32_on = false;
+    }
+    void vcycle_mixed(const T* in, T* out); // mg_solve.hip: scale + round down, the shadow's V-cycle, widen + scale back
+    void fold_shadow_stats() // vcycles and linear_iterations of the shadow's operators count in this context's hot_stats
+    {
+        stats.vcycles += mg32->stats.vcycles, stats.linear_iterations += mg32->stats.linear_iterations;
+        mg32->stats.vcycles = 0, mg32->stats.linear_iterations = 0;
+    }
+    // y (ny values, caller's memory) := op applied to x (nx values, caller's memory) on the shadow: rounded to nearest going in, widened coming out
+    template <class Fn>
+    void mixed_apply(const void* x, size_t nx, void* y, size_t ny, Fn&& op)
+    {
+        if constexpr (sizeof(T) == 8) {
+            DBuf<T> a, b;
+            a.reserve(nx), b.reserve(ny);
+            HOT_HIP(hipMemcpyAsync(a.p, x, nx * sizeof(T), hipMemcpyDefault, stream));
+            mg32->mg32_io[0].reserve(nx), mg32->mg32_io[1].reserve(ny);
+            narrow_dev(nx, a.p, mg32->mg32_io[0].p);
+            op(mg32->mg32_io[0].p, mg32->mg32_io[1].p);
+            widen_dev(ny, mg32->mg32_io[1].p, b.p);
+            download(y, b.p, ny);
+            sync();
+        }
+    }
+    void widen_dev(size_t n, const float* x, double* y); // y := x (mg_solve.hip)
+    void narrow_dev(size_t n, const double* x, float* y); // y := x rounded to nearest
+
+    Ctx(const hot_config& c, hipStream_t borrowed = nullptr); // borrowed: the stream of the context that owns this one (is_shadow)
     ~Ctx();
     template <class U>
     void upload(DBuf<U>& dst, const void* src, size_t n)
@@ -448,6 +505,11 @@ struct Ctx : CtxBase {
         gs_chain_timed_out = false, steps_since_timeout = 0;
         if (!sharded()) gs_no_chain = false; // (several ranks: launch-per-pass sweeps whatever happened, set_comm)
     }
+    void rearm_all() // hot_begin_step: this context's chained path and the shadow's
+    {
+        rearm_chain();
+        if (mg32) mg32->rearm_chain();
+    }
     int n_cu = 0; // compute units of the device (persistent kernels size their grids by it)
     int device_cus()
     {
@@ -466,6 +528,9 @@ struct Ctx : CtxBase {
         // A/B build: HOT_GS_FAKE_TIMEOUT=n raises the time-out flag at the n-th synchronisation inside an operation that can retry — the
         // redo-from-saved-inputs path then runs in a test (tests/test_gpu_variants.py) without a kernel that really hangs
         if (retry_scope > 0 && !gs_no_chain && ab_int("HOT_GS_FAKE_TIMEOUT", 0) > 0 && ++fake_syncs == ab_int("HOT_GS_FAKE_TIMEOUT", 0)) *(volatile int*)(hscal + 250) = 1;
+        // (the same for the flag of the fp32 hierarchy's context: HOT_GS_FAKE_TIMEOUT_SHADOW, tests/test_gpu_mixed_precision.py)
+        if (retry_scope > 0 && mg32 && mg32_on && !mg32->gs_no_chain && ab_int("HOT_GS_FAKE_TIMEOUT_SHADOW", 0) > 0 && ++fake_syncs == ab_int("HOT_GS_FAKE_TIMEOUT_SHADOW", 0)) *(volatile int*)(mg32->hscal + 250) = 1;
+        if (shadow_timed_out()) mg32->sync(); // mixed precision: the shadow books its time-out (path switch, count, deterministic rule) and throws ERR_RETRY through this context's operation
         if (*(volatile int*)(hscal + 250) != 0) {
             *(volatile int*)(hscal + 250) = 0;
             cg_bar_dirty = true; // a k_cg_persist workgroup that gave up did not re-arm the barrier counters: cleared before the next persistent launch (after rearm_chain)
@@ -476,6 +541,7 @@ struct Ctx : CtxBase {
                 throw Error{ ERR_RETRY, "k_gs_sweep: wait on a neighbouring block timed out; deterministic mode: redoing the operation with the same launch structure" };
             }
             gs_no_chain = gs_chain_timed_out = true;
+            if (mg32) mg32->gs_no_chain = mg32->gs_chain_timed_out = true, mg32->steps_since_timeout = 0; // the redo runs the shadow's sweeps with launches too
             throw Error{ ERR_RETRY, "k_gs_sweep: wait on a neighbouring block timed out; redoing the operation with one launch per pass" };
         }
     }
@@ -529,12 +595,14 @@ struct Ctx : CtxBase {
     void get_matrix(int32_t level, int32_t* entryCol, void* entryVal) override;
     long long get_level_nnzb(int32_t level) override
     {
+        if (mixed() && level >= 1) return mg32->get_level_nnzb(level); // mixed precision: levels >= 1 exist only in the fp32 hierarchy
         need(level >= 0 && level < (int)levels.size(), "level out of range");
         if (levels[level]->nnzb < 0) count_nnzb(*levels[level]); // one pass over the values, only when somebody asks
         return levels[level]->nnzb;
     }
     long long get_level_inblock_nnzb(int32_t level) override
     {
+        if (mixed()) return mg32->get_level_inblock_nnzb(level); // mixed precision: only the fp32 hierarchy is coloured
         need(level >= 0 && level < (int)levels.size() && levels[level]->split, "hot_get_level_inblock_nnzb: level out of range or not coloured (hot_build_mg)");
         Level<T>& L = *levels[level];
         std::vector<int32_t> rc(4 * (size_t)L.n);

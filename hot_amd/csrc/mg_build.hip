@@ -1070,9 +1070,130 @@ void Ctx<T>::level0_ownership()
     gs_no_chain = true; // a chained sweep's timeout would be rank-local and desynchronise the collectives
 }
 
+// ------------------------------------------------------------------------------------------------ mixed precision
+// Level 0 of the fp32 hierarchy: the assembled fp64 matrix rounded to nearest, entry by entry.  One streaming pass (C2: 2.6 GB in, 1.3 GB out): a lane
+// reads four consecutive entries with two 16-byte loads and writes them with one 16-byte store, every piece touched once.  NT: the non-temporal hint
+// on both sides (it helps the 16-byte-per-lane copy kernel and hurts 8-byte-per-lane matrix streams, see nt_load; which it is here is measured:
+// profiles/mg_precision.txt).  A value that is not finite after the rounding raises the flag word (pinned host memory, read at the build's sync).
+typedef double hot_d2 __attribute__((ext_vector_type(2)));
+typedef float hot_f4 __attribute__((ext_vector_type(4)));
+template <bool NT>
+__global__ __launch_bounds__(256) void k_mg32_matrix(const double* __restrict__ in, float* __restrict__ out, size_t n, int* bad)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, n4 = n >> 2;
+    bool ok = true;
+    if (i < n4) {
+        const hot_d2* src = (const hot_d2*)in + 2 * i;
+        hot_d2 a, b;
+        if constexpr (NT)
+            a = __builtin_nontemporal_load(src), b = __builtin_nontemporal_load(src + 1);
+        else
+            a = src[0], b = src[1];
+        hot_f4 f;
+        f.x = (float)a.x, f.y = (float)a.y, f.z = (float)b.x, f.w = (float)b.y;
+        ok = (f.x - f.x == 0.0f) && (f.y - f.y == 0.0f) && (f.z - f.z == 0.0f) && (f.w - f.w == 0.0f); // finite
+        if constexpr (NT)
+            __builtin_nontemporal_store(f, (hot_f4*)out + i);
+        else
+            ((hot_f4*)out)[i] = f;
+    }
+    else if (i == n4) { // the (at most three) entries behind the last whole piece
+        for (size_t e = 4 * n4; e < n; ++e) {
+            const float f = (float)in[e];
+            ok = ok && (f - f == 0.0f);
+            out[e] = f;
+        }
+    }
+    if (!ok) *bad = 1;
+}
+
+template <class T>
+void Ctx<T>::check_mixed_allowed()
+{
+    need(!sharded(), "preconditioner dtype 0 (fp32 hierarchy in an fp64 context) is a single-rank mode: a communicator of size > 1 is not supported with it");
+    need(!cfg.useBaselineMultigrid, "preconditioner dtype 0 (fp32 hierarchy in an fp64 context) does not combine with useBaselineMultigrid: its coarse levels are fp64 grids of their own");
+    need(!cfg.matrixFree, "preconditioner dtype 0 (fp32 hierarchy in an fp64 context) does not combine with matrixFree: there is no assembled matrix to round");
+}
+template <class T>
+void Ctx<T>::set_preconditioner_dtype(int32_t dtype)
+{
+    need(dtype == 0 || dtype == 1, "hot_set_preconditioner_dtype: dtype must be 1 (the context's own precision) or 0 (fp32)");
+    if (sizeof(T) == 4) {
+        need(dtype == 0, "hot_set_preconditioner_dtype: an fp64 hierarchy under an fp32 context is not supported (dtype 1 in a dtype 0 context)");
+        return;
+    }
+    if (dtype == 0) check_mixed_allowed();
+    precond_dtype = dtype;
+}
+
+template <class T>
+void Ctx<T>::build_mg_mixed()
+{
+    if constexpr (sizeof(T) == 8) {
+        need(!levels.empty(), "hot_build_mg before hot_build_hessian");
+        check_mixed_allowed();
+        need(cfg.systemBCProject != 0, "preconditioner dtype 0 (fp32 hierarchy in an fp64 context) requires systemBCProject: the fp32 smoothers have no boundary projection of their own");
+        const double t0 = wall_ms();
+        mg32_on = false;
+        release_levels(1);
+        Level<T>& L0 = *levels[0];
+        need(!L0.split, "hot_build_mg with preconditioner dtype 0 after an fp64 hot_build_mg on the same matrix: the fp64 build regrouped the rows of level 0, call hot_build_hessian first");
+        // what an fp64 hot_build_mg left on this context: nothing of it is read in mixed mode (1.7 GB of images at C2)
+        if (L0.gs_col.p || L0.residual.p || L0.apv.p) sync(), L0.release_hierarchy();
+        for (int id = 0; id < 12; ++id)
+            for (size_t k = level_pool[id].size(); k-- > 0;) {
+                if (id == 0) {
+                    if (level_pool[0][k]->gs_col.p || level_pool[0][k]->apv.p) level_pool[0][k]->release_hierarchy();
+                    continue;
+                }
+                delete level_pool[id][k];
+                level_pool[id].erase(level_pool[id].begin() + (long)k);
+            }
+        if (col_hk.p || cg_dep.p || ap.p) // (and the build / top-solver scratch that goes with it)
+            sync(), col_hk.release(), col_hr.release(), col_hi.release(), col_cb.release(), cg_dep.release(), ap.release();
+        hot_config c32 = cfg;
+        c32.dtype = 0;
+        if (!mg32) {
+            mg32 = new Ctx<float>(c32, stream);
+            mg32->in_scale_h = hscal + 252;
+            prof_child = mg32;
+        }
+        mg32->cfg = c32;
+        mg32->release_levels(0);
+        Level<float>* S = mg32->acquire_level(0);
+        mg32->levels.push_back(S);
+        const size_t n = (size_t)L0.n, ne = n * 125;
+        S->n = L0.n, S->built = false, S->split = false, S->part = false, S->colored = false;
+        mg32->Nn = L0.n;
+        S->coord.reserve(3 * n), S->col.reserve(ne), S->val.reserve(ne * 9);
+        HOT_HIP(hipMemcpyAsync(S->coord.p, L0.coord.p, 3 * n * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        HOT_HIP(hipMemcpyAsync(S->col.p, L0.col.p, ne * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        int* bad = (int*)(hscal + 253);
+        *(volatile int*)bad = 0;
+        const int grid = div_up((ne * 9 >> 2) + 1, 256);
+        if (ab_flag("HOT_MG32_NT"))
+            HOT_LAUNCH(this, "mg32_matrix", k_mg32_matrix<true>, grid, 256, 0, L0.val.p, S->val.p, ne * 9, bad);
+        else
+            HOT_LAUNCH(this, "mg32_matrix", k_mg32_matrix<false>, grid, 256, 0, L0.val.p, S->val.p, ne * 9, bad);
+        mg32->build_diagonal(*S);
+        S->nnzb = -1;
+        const double before = mg32->stats.ms_mg_build;
+        mg32->build_mg(); // Galerkin products, colouring, row regrouping, images, slot lists and A P, all in fp32; ends with a stream synchronisation
+        mg32->stats.ms_mg_build = before;
+        HOT_CHECK(*(volatile int*)bad == 0, HOT_ERR_NUMERIC, "hot_build_mg: an entry of the fp64 matrix is not finite after rounding to fp32 (preconditioner dtype 0)");
+        mg32_on = true;
+        stats.ms_mg_build += wall_ms() - t0;
+    }
+}
+
 template <class T>
 void Ctx<T>::build_mg()
 {
+    if (sizeof(T) == 8 && precond_dtype == 0 && !is_shadow) {
+        build_mg_mixed();
+        return;
+    }
+    if (mg32_on) drop_mixed(); // switched back: the fp32 hierarchy goes back to the shadow's pool
     need(!levels.empty(), "hot_build_mg before hot_build_hessian");
     need(!(!cfg.systemBCProject && cfg.levelCnt > 1), "levelCnt > 1 requires systemBCProject (ImplicitSolver.h:339)");
     need(cfg.levelCnt >= 1 && cfg.levelCnt <= 10, "levelCnt must be in [1,10] (MultigridPreconditioner.h:369)");
@@ -1194,6 +1315,10 @@ void Ctx<T>::build_mg()
 template <class T>
 void Ctx<T>::get_level(int32_t level, int32_t* nrows, int32_t* colsize, int32_t* ic)
 {
+    if (mixed() && level >= 1) { // mixed precision: levels >= 1 exist only in the fp32 hierarchy
+        mg32->get_level(level, nrows, colsize, ic);
+        return;
+    }
     need(level >= 0 && level < (int)levels.size(), "level out of range");
     Level<T>& L = *levels[level];
     if (nrows) *nrows = L.n;
@@ -1204,6 +1329,18 @@ void Ctx<T>::get_level(int32_t level, int32_t* nrows, int32_t* colsize, int32_t*
 template <class T>
 void Ctx<T>::get_matrix(int32_t level, int32_t* entryCol, void* entryVal)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed() && level >= 1) { // the fp32 data, widened
+            need(level < nlevels(), "level out of range");
+            Level<float>& S = *mg32->levels[level];
+            DBuf<T> w;
+            w.reserve(1125 * (size_t)S.n);
+            widen_dev(1125 * (size_t)S.n, S.val.p, w.p);
+            download(entryCol, S.col.p, 125 * (size_t)S.n);
+            download(entryVal, w.p, 1125 * (size_t)S.n);
+            sync();
+            return;
+        }
     need(level >= 0 && level < (int)levels.size(), "level out of range");
     Level<T>& L = *levels[level];
     download(entryCol, L.col.p, 125 * (size_t)L.n);
@@ -1213,6 +1350,18 @@ void Ctx<T>::get_matrix(int32_t level, int32_t* entryCol, void* entryVal)
 template <class T>
 void Ctx<T>::get_prolongation(int32_t level, int32_t* entryCol, void* weight)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed()) { // the transfer tables exist only in the fp32 hierarchy
+            need(level >= 0 && level + 1 < nlevels(), "level out of range");
+            Level<float>& S = *mg32->levels[level];
+            DBuf<T> w;
+            w.reserve(8 * (size_t)S.n);
+            widen_dev(8 * (size_t)S.n, S.pw.p, w.p);
+            download(entryCol, S.pcol.p, 8 * (size_t)S.n);
+            download(weight, w.p, 8 * (size_t)S.n);
+            sync();
+            return;
+        }
     need(level >= 0 && level + 1 < (int)levels.size(), "level out of range");
     Level<T>& L = *levels[level];
     download(entryCol, L.pcol.p, 8 * (size_t)L.n);

@@ -85,6 +85,105 @@ __global__ __launch_bounds__(256) void k_vcycle_start(size_t n, const T* __restr
         if (y2) y2[i] = v;
     }
 }
+// ---- mixed precision: the fp64 vectors that enter and leave the fp32 V-cycle.
+// y := x converted (round to nearest going down, exact going up): the vectors of hot_smooth / hot_restrict / hot_prolong / hot_spmv, exported fp32 data
+template <class A, class B>
+__global__ __launch_bounds__(256) void k_mg32_convert(size_t n, const A* __restrict__ x, B* __restrict__ y)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = (B)x[i];
+}
+// The largest magnitude of x and from it sc[0] = 2^-e, sc[1] = 2^e with 2^e <= max |x| < 2^(e+1) (e = 0 for an infinite maximum; fmax drops a NaN, so an x with NaN among finite entries is scaled by the finite maximum and the NaN goes through the V-cycle as it would in fp64; sc[1] = 0 marks an all-zero x; clamped to the
+// exponents of normal numbers).  One launch, grid_sum_store's hand-off with a maximum in the place of the sum: every workgroup deposits its maximum, the
+// one that arrives last takes the maximum of the deposits (exact in any order) and stores the scales; no floating-point atomics.  mirror: pinned host word
+// that receives 2^e too (the absolute stopping test of a Jacobi top solver, smooth_dev kind 1, is applied to the unscaled residual).
+__global__ __launch_bounds__(256) void k_mg32_absmax(size_t n, const double* __restrict__ x, GridRed gr, double* sc, double* mirror)
+{
+    __shared__ double red[4];
+    __shared__ int s_last;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    auto block_max = [&](double m) {
+        for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+        if (lane == 0) red[w] = m;
+        __syncthreads();
+        const double r = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+        __syncthreads();
+        return r;
+    };
+    double m = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmax(m, fabs(x[i]));
+    m = block_max(m);
+    const unsigned nb = gridDim.x;
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(gr.part + blockIdx.x, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned prev = __hip_atomic_fetch_add(gr.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = prev == nb - 1u;
+    }
+    __syncthreads();
+    if (!s_last) return; // workgroup-uniform
+    double a = 0;
+    for (unsigned i = threadIdx.x; i < nb; i += 256) a = fmax(a, __hip_atomic_load(gr.part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    a = block_max(a);
+    if (threadIdx.x == 0) {
+        int e = (a > 0.0 && a < (double)INFINITY) ? ilogb(a) : 0;
+        e = e < -1022 ? -1022 : e;
+        const double down = scalbn(1.0, -e), up = scalbn(1.0, e);
+        sc[0] = down, sc[1] = a == 0.0 ? 0.0 : up; // (an all-zero input: the exit writes zeros whatever the fp32 solvers made of a zero residual, 0 / 0 in the PCG's step length)
+        if (mirror) *mirror = up; // a plain store: the host reads it only after the ticket of a later kernel on this stream (smooth_dev's round trip), which orders it
+        __hip_atomic_store(gr.count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// k_vcycle_start of the fp32 hierarchy fed from an fp64 vector: y := float(x 2^-e), y2 := the same (if not null), z := 0
+__global__ __launch_bounds__(256) void k_mg32_enter(size_t n, const double* __restrict__ x, const double* __restrict__ sc, float* __restrict__ y, float* __restrict__ y2, float* __restrict__ z)
+{
+    const double down = sc[0];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float v = (float)(x[i] * down); // the product is exact (a power of two, no underflow above the smallest fp32 subnormal's range), one rounding
+        y[i] = v, z[i] = 0.0f;
+        if (y2) y2[i] = v;
+    }
+}
+// out := double(z) 2^e (exact); zeros for an all-zero input
+__global__ __launch_bounds__(256) void k_mg32_exit(size_t n, const float* __restrict__ z, const double* __restrict__ sc, double* __restrict__ out)
+{
+    const double up = sc[1]; // 0: the input was all zero
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = up == 0.0 ? 0.0 : (double)z[i] * up;
+}
+template <class T>
+void Ctx<T>::widen_dev(size_t n, const float* x, double* y)
+{
+    if (n) HOT_LAUNCH(this, "mg32_convert", (k_mg32_convert<float, double>), (int)std::min<size_t>(div_up(n, 256), 4096), 256, 0, n, x, y);
+}
+template <class T>
+void Ctx<T>::narrow_dev(size_t n, const double* x, float* y)
+{
+    if (n) HOT_LAUNCH(this, "mg32_convert", (k_mg32_convert<double, float>), (int)std::min<size_t>(div_up(n, 256), 4096), 256, 0, n, x, y);
+}
+// The preconditioner of an fp64 context on the fp32 hierarchy: one reduction launch for the scale, the shadow's V-cycle with k_mg32_enter as its head
+// (in the place of k_vcycle_start), one launch that widens and scales back.  The exponent never leaves the device.
+template <class T>
+void Ctx<T>::vcycle_mixed(const T* in, T* out)
+{
+    if constexpr (sizeof(T) == 8) {
+        const size_t n0 = 3 * (size_t)mg32->levels[0]->n;
+        double* sc = dscal.p + 230;
+        const int grid = std::min(div_up(n0, 1024), 256);
+        HOT_LAUNCH(this, "mg32_enter", k_mg32_absmax, grid, 256, 0, n0, in, gred(grid), sc, hscal + 252);
+        mg32->mg32_io[0].reserve(n0);
+        float* out32 = mg32->mg32_io[0].p;
+        mg32->vcycle_head = [this, in, sc, n0](float* y, float* y2, float* z) {
+            HOT_LAUNCH(this, "mg32_enter", k_mg32_enter, (int)std::min<size_t>(div_up(n0, 256), 2048), 256, 0, n0, in, sc, y, y2, z);
+        };
+        struct Unhook {
+            Ctx<float>* c;
+            ~Unhook() { c->vcycle_head = nullptr; }
+        } unhook{ mg32 };
+        mg32->vcycle_dev(nullptr, out32);
+        fold_shadow_stats();
+        HOT_LAUNCH(this, "mg32_exit", k_mg32_exit, (int)std::min<size_t>(div_up(n0, 256), 2048), 256, 0, n0, out32, sc, out);
+    }
+}
+
 template <class T>
 void Ctx<T>::copy(size_t n, const T* x, T* y)
 {
@@ -829,7 +928,7 @@ void Ctx<T>::smooth_dev(int level, int kind, int iterations, T tolerance, T* u, 
     else if (kind == 1) {
         for (; iterations--;) {
             double rr = dot_host(n3, r, r);
-            if (std::sqrt(rr) < (double)tolerance) break;
+            if (std::sqrt(rr) * (in_scale_h ? *in_scale_h : 1.0) < (double)tolerance) break; // (the shadow of a mixed-precision context: the test is on the unscaled residual)
             scaler(r, du);
             spmv_dev(L, du, dAu);
             Aproject(dAu);
@@ -973,6 +1072,10 @@ void Ctx<T>::smooth_dev(int level, int kind, int iterations, T tolerance, T* u, 
 template <class T>
 void Ctx<T>::vcycle_dev(const T* in, T* out)
 {
+    if (mixed()) { // mixed precision: every V-cycle of this context (L-BFGS's initial Hessian, the Newton solvers' M^-1, hot_vcycle) runs on the fp32 hierarchy
+        vcycle_mixed(in, out);
+        return;
+    }
     int levelCnt = (int)levels.size();
     int times = cfg.times, levelscale = cfg.levelscale;
     int splitLevel;
@@ -996,7 +1099,11 @@ void Ctx<T>::vcycle_dev(const T* in, T* out)
     size_t n0 = 3 * (size_t)L0.n;
     // residual := in (dRhs == 0, ImplicitSolver.h:483-484,579: correctResidualProjection is the identity), out := 0 and, on a single level, the
     // top solver's initial residual: one launch instead of two copies and a fill
+    if (vcycle_head) // the shadow of a mixed-precision context: its parent's fp64 vector, scaled and rounded (k_mg32_enter)
+        vcycle_head(L0.residual.p, levelCnt > 1 ? (T*)nullptr : L0.initialResidual.p, out);
+    else
     HOT_LAUNCH(this, "vcycle_start", k_vcycle_start<T>, (int)std::min<size_t>(div_up(n0, 256), 2048), 256, 0, n0, in, L0.residual.p, levelCnt > 1 ? (T*)nullptr : L0.initialResidual.p, out);
+
     if (levelCnt > 1) restrict_dev(0, L0.residual.p, levels[1]->initialResidual.p);
     for (int l = 1; l < levelCnt - 1; ++l) restrict_dev(l, levels[l]->initialResidual.p, levels[l + 1]->initialResidual.p);
     int level;
@@ -1032,7 +1139,7 @@ void Ctx<T>::vcycle_dev(const T* in, T* out)
 template <class T>
 void Ctx<T>::precondition_dev(const T* in, T* out)
 {
-    HOT_CHECK(!levels.empty() && levels[0]->built, HOT_ERR_INVALID, "preconditioner used before hot_build_mg");
+    HOT_CHECK(mixed() || (!levels.empty() && levels[0]->built), HOT_ERR_INVALID, "preconditioner used before hot_build_mg");
     vcycle_dev(in, out);
 }
 
@@ -1040,6 +1147,13 @@ void Ctx<T>::precondition_dev(const T* in, T* out)
 template <class T>
 void Ctx<T>::spmv(int32_t level, const void* x, void* y)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed() && level >= 1) { // mixed precision: levels >= 1 exist only in fp32 (level 0 stays the fp64 Hessian: the operator of the Newton solvers)
+            need(level < nlevels(), "level out of range");
+            Level<float>& S = *mg32->levels[level];
+            mixed_apply(x, 3 * (size_t)S.n, y, 3 * (size_t)S.n, [&](float* a, float* b) { mg32->spmv_dev(S, a, b); });
+            return;
+        }
     need(level >= 0 && level < (int)levels.size(), "level out of range");
     Level<T>& L = *levels[level];
     size_t n3 = 3 * (size_t)L.n;
@@ -1054,6 +1168,12 @@ void Ctx<T>::spmv(int32_t level, const void* x, void* y)
 template <class T>
 void Ctx<T>::restrict_(int32_t level, const void* fine, void* coarse)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed()) {
+            need(level >= 0 && level + 1 < nlevels(), "level out of range");
+            mixed_apply(fine, 3 * (size_t)mg32->levels[level]->n, coarse, 3 * (size_t)mg32->levels[level + 1]->n, [&](float* a, float* b) { mg32->restrict_dev(level, a, b), mg32->unset_level = -1; });
+            return;
+        }
     need(level >= 0 && level + 1 < (int)levels.size(), "level out of range");
     size_t nf = 3 * (size_t)levels[level]->n, nc = 3 * (size_t)levels[level + 1]->n;
     DBuf<T> a, b;
@@ -1067,6 +1187,12 @@ void Ctx<T>::restrict_(int32_t level, const void* fine, void* coarse)
 template <class T>
 void Ctx<T>::prolong(int32_t level, const void* coarse, void* fine)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed()) {
+            need(level >= 0 && level + 1 < nlevels(), "level out of range");
+            mixed_apply(coarse, 3 * (size_t)mg32->levels[level + 1]->n, fine, 3 * (size_t)mg32->levels[level]->n, [&](float* a, float* b) { mg32->prolong_dev(level, a, b); });
+            return;
+        }
     need(level >= 0 && level + 1 < (int)levels.size(), "level out of range");
     size_t nf = 3 * (size_t)levels[level]->n, nc = 3 * (size_t)levels[level + 1]->n;
     DBuf<T> a, b;
@@ -1080,6 +1206,30 @@ void Ctx<T>::prolong(int32_t level, const void* coarse, void* fine)
 template <class T>
 void Ctx<T>::smooth(int32_t level, int32_t kind, int32_t iterations, double tol, void* u, void* r, const void* r0)
 {
+    if constexpr (sizeof(T) == 8)
+        if (mixed()) { // the fp32 operators on every level, level 0 included; u, r, r0 rounded to nearest on the way in, widened on the way out
+            need(level >= 0 && level < nlevels() && mg32->levels[level]->built, "hot_smooth: level not built (hot_build_mg)");
+            Level<float>& S = *mg32->levels[level];
+            const size_t n3 = 3 * (size_t)S.n;
+            DBuf<T> keep[3];
+            for (auto& k : keep) k.reserve(n3);
+            HOT_HIP(hipMemcpyAsync(keep[0].p, u, n3 * sizeof(T), hipMemcpyDefault, stream));
+            HOT_HIP(hipMemcpyAsync(keep[1].p, r, n3 * sizeof(T), hipMemcpyDefault, stream));
+            HOT_HIP(hipMemcpyAsync(keep[2].p, r0 ? r0 : r, n3 * sizeof(T), hipMemcpyDefault, stream));
+            for (auto& b : mg32->mg32_io) b.reserve(n3);
+            hscal[252] = 1.0; // nothing was scaled: absolute stopping tests as they stand
+            with_gs_retry([&] {
+                narrow_dev(n3, keep[0].p, mg32->mg32_io[0].p), narrow_dev(n3, keep[1].p, mg32->mg32_io[1].p), narrow_dev(n3, keep[2].p, S.initialResidual.p);
+                mg32->smooth_dev(level, kind, iterations, (float)tol, mg32->mg32_io[0].p, mg32->mg32_io[1].p, S.du.p, S.dAu.p);
+                fold_shadow_stats();
+                sync();
+            });
+            widen_dev(n3, mg32->mg32_io[0].p, keep[0].p), widen_dev(n3, mg32->mg32_io[1].p, keep[1].p);
+            download(u, keep[0].p, n3);
+            download(r, keep[1].p, n3);
+            sync();
+            return;
+        }
     need(level >= 0 && level < (int)levels.size() && levels[level]->built, "hot_smooth: level not built (hot_build_mg)");
     Level<T>& L = *levels[level];
     size_t n3 = 3 * (size_t)L.n;
@@ -1101,7 +1251,7 @@ void Ctx<T>::smooth(int32_t level, int32_t kind, int32_t iterations, double tol,
 template <class T>
 void Ctx<T>::vcycle(const void* in, void* out)
 {
-    need(!levels.empty() && levels[0]->built, "hot_vcycle before hot_build_mg");
+    need(mixed() || (!levels.empty() && levels[0]->built), "hot_vcycle before hot_build_mg");
     size_t n3 = 3 * (size_t)Nn;
     HOT_HIP(hipMemcpyAsync(work0.p, in, n3 * sizeof(T), hipMemcpyDefault, stream));
     with_gs_retry([&] {

@@ -22,6 +22,7 @@ void Ctx<T>::set_comm(const hot_comm* c)
         need(c->allreduce && c->allgather && c->alltoallv, "hot_set_comm: all three collectives are required");
         need(c->rank >= 0 && c->rank < c->size && c->size <= 64, "hot_set_comm: 0 <= rank < size <= 64");
         need(!cfg.useBaselineMultigrid, "hot_set_comm: the --baseline geometric multigrid is single-rank only");
+        need(!(sizeof(T) == 8 && precond_dtype == 0), "hot_set_comm: preconditioner dtype 0 (fp32 hierarchy in an fp64 context) is a single-rank mode: a communicator of size > 1 is not supported with it");
         comm = *c;
         gs_no_chain = true; // a chained coarse-level sweep that timed out would make ONE rank redo its solve and desynchronise the collectives: launch-per-pass sweeps only
     }

@@ -728,9 +728,9 @@ void Ctx<T>::solve(hot_stats* st)
             newton_solve();
         sync();
     });
-    prof.collect();
+    prof_collect();
     stats.num_nodes = Nn;
-    stats.num_levels = (halo_mode() && cfg.matrixFree) ? 0 : (int)levels.size(); // halo mode keeps a matrix-less level 0 (row ownership, exchange lists) also for the matrix-free solvers
+    stats.num_levels = (halo_mode() && cfg.matrixFree) ? 0 : nlevels(); // halo mode keeps a matrix-less level 0 (row ownership, exchange lists) also for the matrix-free solvers
     stats.energy = cfg.linesearch ? Ek : 0.0; // the incremental potential at the last accepted line-search point; without a line search nobody evaluates it there (ImplicitSolver.h:237-252)
     stats.ms_solve = wall_ms() - t0;
     export_comm_stats();

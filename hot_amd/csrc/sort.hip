@@ -241,12 +241,15 @@ __global__ void k_group_ranges(const int32_t* __restrict__ first, int32_t* out, 
 
 // ------------------------------------------------------------------------------------------------ Ctx
 template <class T>
-Ctx<T>::Ctx(const hot_config& c)
+Ctx<T>::Ctx(const hot_config& c, hipStream_t borrowed)
 {
     cfg = c;
     dx = (T)c.dx;
     HOT_HIP(hipSetDevice(c.device));
-    HOT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    if (borrowed)
+        stream = borrowed, is_shadow = true; // a context inside a context (mixed precision): the parent's stream, never destroyed here
+    else
+        HOT_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     prof.on = c.profile != 0;
     keep_debug = c.debug_store != 0;
     dscal.reserve(1024); // [0,256) solver scalars, [512, 1024) L-BFGS two-loop: dot batches and the Gram matrix (solve.hip)
@@ -259,12 +262,13 @@ Ctx<T>::Ctx(const hot_config& c)
 template <class T>
 Ctx<T>::~Ctx()
 {
+    delete mg32;
     for (auto* g : gmg) delete g;
     for (auto* l : levels) delete l;
     for (auto& pool : level_pool)
         for (auto* l : pool) delete l;
     if (hscal) (void)hipHostFree(hscal);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (stream && !is_shadow) (void)hipStreamDestroy(stream);
 }
 
 template <class T>

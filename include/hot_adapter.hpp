@@ -88,6 +88,15 @@ public:
     {
         check(ctx, hot_set_plasticity_classes(ctx, n, classes, particle_class), "hot_set_plasticity_classes");
     }
+    // precision of the multigrid hierarchy the preconditioner runs on: 1 = the context's own (default), 0 = fp32 inside an fp64 context; takes effect at
+    // the next hot_build_mg (include/hot_mi355x.h, "mixed precision")
+    void setPreconditionerDtype(int dtype) { check(ctx, hot_set_preconditioner_dtype(ctx, dtype), "hot_set_preconditioner_dtype"); }
+    int preconditionerDtype()
+    {
+        int32_t d = 1;
+        check(ctx, hot_get_preconditioner_dtype(ctx, &d), "hot_get_preconditioner_dtype");
+        return d;
+    }
     void getParticles(T* X, T* V, T* C, T* F, T* mu = nullptr, T* lambda = nullptr, T* Jp = nullptr) { check(ctx, hot_get_particles(ctx, X, V, C, F, mu, lambda, Jp), "hot_get_particles"); }
     void sortParticlesAndPolluteGrid() { check(ctx, hot_sort(ctx), "hot_sort"); }
     void particlesToGrid() { check(ctx, hot_p2g(ctx), "hot_p2g"); }

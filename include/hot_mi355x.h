@@ -374,6 +374,31 @@ int hot_set_plasticity_classes(hot_ctx*, int32_t n, const hot_plasticity_class* 
 int hot_get_plasticity_classes(hot_ctx*, int32_t* n, hot_plasticity_class* classes /*>= 16, or NULL*/, int32_t* particle_class /*Np, or NULL*/);
 int hot_plasticity_eval_classes(hot_ctx*, int32_t n, void* F /*9n in/out*/, void* mu /*n in/out*/, void* lambda /*n in/out*/, void* Jp /*n in/out*/, const int32_t* cls /*n*/);
 
+/* ---- mixed precision (HIP product only): the precision of the multigrid hierarchy the preconditioner runs on.
+ *      dtype 1 = the context's own (default), 0 = an fp32 hierarchy inside an fp64 context: the V-cycle is only the preconditioner (the initial Hessian
+ *      of L-BFGS, the M^-1 of the projected-Newton PCG / MINRES); energies, line search, residual, exit test, curvature pairs and particle state
+ *      never read a hierarchy matrix and stay fp64, while every traffic-bound V-cycle kernel moves half the bytes.
+ *      Callable any time after hot_create; takes effect at the next hot_build_mg (those hot_solve / hot_advance issue and the useAdaptiveHessian
+ *      rebuilds included); setting 1 again releases the fp32 hierarchy at the next build.  In a dtype 0 context 0 is accepted and changes nothing and 1
+ *      is HOT_ERR_INVALID; any other value is HOT_ERR_INVALID.  HOT_ERR_INVALID with a message that names the reason, at the call or at the first
+ *      hot_build_mg where the combination becomes known: a communicator of size > 1, useBaselineMultigrid, matrixFree, systemBCProject = 0 (the
+ *      fp32 smoothers have no boundary projection of their own), and a hot_build_mg that follows an fp64 hot_build_mg without a hot_build_hessian in
+ *      between (the fp64 build regrouped the rows of level 0; hot_solve / hot_advance always assemble first).  Everything else an fp32
+ *      context supports is allowed (every smoother and coarse solver, topDownMGS, times, levelscale, gs_chain, gs_sub_block, deterministic,
+ *      lsolver 1 / 2 / 3); with Ainv = 2 there is no hierarchy and the switch has nothing to act on.
+ *      What the hierarchy calls mean in mixed mode:
+ *        hot_get_matrix(0), hot_spmv(0)   the assembled fp64 Hessian (the operator of the Newton solvers: Amul keeps multiplying with it in fp64); it
+ *                                        stays in stencil-slot order, hot_build_mg prepares no fp64 Gauss-Seidel structure on it.  hot_get_level(0) is unchanged.
+ *        level 0 of the preconditioner   that matrix rounded to nearest fp32, entry by entry; an entry that is not finite after the rounding makes
+ *                                        hot_build_mg fail with HOT_ERR_NUMERIC.
+ *        levels >= 1                     exist only in fp32: hot_get_level, hot_get_matrix, hot_get_prolongation, hot_get_level_nnzb and hot_spmv return /
+ *                                        use the fp32 data, values widened to real = double.
+ *        hot_smooth, hot_restrict, hot_prolong, hot_vcycle   run the fp32 operators on every level, level 0 included; vectors are converted at the boundary.
+ *      The V-cycle's input is scaled by the power of two that brings its largest magnitude into [1, 2) before it is rounded to fp32 and the output is scaled
+ *      back (both exact), so the fp32 V-cycle sees the same bits whatever the magnitude of the residual; an all-zero input gives an all-zero output. */
+int hot_set_preconditioner_dtype(hot_ctx*, int32_t dtype);
+int hot_get_preconditioner_dtype(hot_ctx*, int32_t* dtype);
+
 /* ---- frame output (SimulationBase::write -> MpmSimulationBase::writeState, Lib/Ziran/Sim/SimulationBase.h:152-190,
  *      Lib/MPM/MpmSimulationBase.cpp:754-785): hot_write_partio = writePartio's .bgeo of the particle positions (PartioIO.h:142-180);
  *      hot_write_restart / hot_read_restart = the particle DataManager in the container layout of DataManager::writeData

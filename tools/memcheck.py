@@ -1,5 +1,5 @@
-"""Check (not a test): device memory in use after 2, 4, 8, 16 time steps (Galerkin and --baseline hierarchies) — buffers are
-grow-only and recycled, so the figure must level off."""
+"""Check (not a test): device memory in use after 2, 4, 8, 16 time steps (Galerkin and --baseline hierarchies, and the fp32 hierarchy of
+mixed precision, whose levels are recycled through the shadow context's own pool) — buffers are grow-only and recycled, so the figure must level off."""
 import os, sys, ctypes
 sys.path.insert(0, os.getcwd())
 import numpy as np
@@ -11,7 +11,7 @@ def used():
     hip.hipMemGetInfo(ctypes.byref(f), ctypes.byref(t))
     return (t.value - f.value) / 2**20
 lib = hot_amd.load()
-for name, kw in (("C2", {}), ("C2-baseline", dict(useBaselineMultigrid=1))):
+for name, kw in (("C2", {}), ("C2-baseline", dict(useBaselineMultigrid=1)), ("C2-mixed", dict(preconditioner_dtype=0))):
     cfg = dict(synth.CONFIGS["C2"])
     cloud = parallel.shard_cloud(cfg, 0, 1, n=cfg["n"])
     ctx = bench.make_ctx(lib, cloud, cfg, **kw)
